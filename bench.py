@@ -26,11 +26,22 @@ all-gather of the per-env episode-end records (return, length, success) of every
 (SURVEY.md 8e): a launch of R env-steps is followed by its R per-env-step gathers.
 
     python bench.py [--gpus N --steps K --warmup W]       (defaults: N 1, K 30, W 2)
+    python bench.py ... --dump-outputs DIR                (the last timed step's outputs as DIR/<name>.npy)
+    python bench.py ... --full                            (every side line and check below)
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints one JSON line.  `roofline.achieved` = algorithmic bytes per launch of
-the fused step kernel (SURVEY.md 8d per-env-substep working set, constants frozen from
-the model below) / the kernel's average duration from HIP events recorded on the
+Rank 0 prints one JSON line.  A plain run sets up (pre-roll included), warms up, times the K
+env-steps and prints the headline: metric, value, unit, ms_per_step (wall ms of one timed
+env-step of the whole batch) and the workload's static description.  --dump-outputs writes what
+the timed path's caller holds after the last timed env-step (obs, reward, done, the launch's
+episode-end records); the inputs depend on the arguments alone, so two builds compare file for
+file.  Everything else is measured only with --full: the per-step API, the roofline and solver
+probes, obs parity against the oracle, the CPU baseline and the C1 / C2 / C3-variant / C5 line
+items (each with its own --no-* switch); its headline also brackets every timed launch with
+the two HIP events the roofline reads, which a plain run does not record (two event records
+per launch of R env-steps, within run-to-run noise).  `roofline.achieved` = algorithmic bytes
+per launch of the fused step kernel (SURVEY.md 8d per-env-substep working set, constants
+frozen from the model below) / the kernel's average duration from HIP events recorded on the
 stream it is launched on.  `cpu_baseline` times the fp64 CPU oracle (a restatement of
 the reference path; the reference bind.so needs MuJoCo 2.1.5 and cannot be built).
 """
@@ -430,6 +441,45 @@ def policy_rollout(gmx, torch, dev, stream, n: int, steps: int, seed: int, env_o
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs writes at most this much in all
+
+
+def timed_outputs(env, episodes) -> dict:
+    """What a caller of the timed path holds after its last drive: obs / reward / done of the
+    last env-step of every env (gm_get_outputs) and the drive's episode-end records
+    (`episodes`, [R, n, 3] int32: return, length, success per env-step of the launch; the
+    return reads 0 where no episode ended)."""
+    import torch
+    from gmx.shard import unpack_episodes
+    obs, rew, done = env.outputs()
+    shape = tuple(episodes.shape[:-1])
+    ret, length, success = unpack_episodes(episodes.reshape(-1, 3))
+    ret = torch.where(length > 0, ret, torch.zeros_like(ret))
+    return {"obs": obs, "reward": rew, "done": done,
+            "episode_return": ret.cpu().numpy().reshape(shape),
+            "episode_length": length.cpu().numpy().reshape(shape),
+            "episode_success": success.cpu().numpy().reshape(shape)}
+
+
+def dump_outputs(path: str, arrays: dict, max_bytes: int = DUMP_MAX_BYTES) -> dict:
+    """Write each array as path/<name>.npy (float64 stays, everything else becomes float32),
+    at most max_bytes in all: an array over its equal share of the budget is cut to a fixed
+    sample of its elements (np.random.default_rng(0), in index order, the same elements for
+    the same shape).  Returns {name: written shape}."""
+    os.makedirs(path, exist_ok=True)
+    share = max_bytes // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def measure(drive, episodes, K: int, W: int, world: int, dev, sync):
     """The contract's timed region, independent of what steps the envs (the device here,
     the oracle in tests/test_distributed.py): W untimed warmup drives, then EXACTLY K
@@ -497,6 +547,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the per-step API, the roofline and solver probes, obs "
+                         "parity, the CPU baseline and the C1/C2/C3-variant/C5 line items (the --no-* switches "
+                         "and --cpu-* / --c2-rollout apply to these); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step (obs, reward, done, episode-end "
+                         "records of the last launch) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-envs", type=int, default=40, help="envs per CPU thread in the baseline")
     ap.add_argument("--cpu-steps", type=int, default=250)
     ap.add_argument("--cpu-threads", type=int, default=16,
@@ -582,7 +639,8 @@ def main():
 
     # steady state: env e (global id) starts its episode at pre-roll step t_e, so after
     # MAX_EP untimed steps the batch covers episode steps 1..MAX_EP uniformly
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(max(K, 1))]
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for _ in range(max(K, 1) if args.full else 0)]
     gids = first_env + np.arange(n)
     t_start = gmx.spawn_int(args.seed, gids, 0, 99, 0, MAX_EP - 1)
     for t in range(MAX_EP if args.preroll else 0):
@@ -591,7 +649,35 @@ def main():
             env.lib.gm_reset(env.ctx, np.ascontiguousarray(m.astype(np.uint8)).ctypes.data_as(
                 __import__("ctypes").POINTER(__import__("ctypes").c_uint8)), None)
         drive_ps()
-    elapsed, ep_stats = measure(drive, episodes, n_drives, w_drives, world, dev, torch.cuda.synchronize)
+    # only --full's roofline reads the kernel's HIP events: a plain run records none
+    elapsed, ep_stats = measure(drive if args.full else (lambda k=None: drive()), episodes, n_drives, w_drives,
+                                world, dev, torch.cuda.synchronize)
+    out = headline(world, n, K, W, elapsed, ep_stats)
+    if args.dump_outputs and rank == 0:      # rank 0's shard, before anything else steps the batch
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, timed_outputs(env, episodes))
+    out["warmup_steps_run"] = max(w_drives, 1) * R
+    out["config"].update({"workload": "C3: set6_synthetic 20 mixed objects, randomised spawn (object drawn per "
+                               "episode, spawn_into_scene grid search on the device), steady state: envs "
+                               "staggered over episode steps 1..250 by an untimed pre-roll, benchmark mix "
+                               "(1 episode in 4: the closed-loop grasp-lift-hold program; otherwise the "
+                               "scripted grasp mix: close / squeeze / palm / lift + jitter), canonical "
+                               "sensor/reward "
+                               "config, device auto-reset at done / 250 steps; driven as gm_rollout launches "
+                               f"of {R} env-steps (driver actions, env-step, episode-end record and reset "
+                               "fused per env; bit-identical to the per-step API, tests/test_rollout.py)"
+                               if rollout else "the per-step API",
+                   "substeps_per_env_step": S,
+                   "model": {"nq": env.model.nq, "nv": env.model.nv, "nbody": env.model.nbody,
+                             "ngeom": env.model.ngeom, "nM": env.model.nM, "nlock": env.model.nlock},
+                   "dtype_detail": "f64 dynamics, collision and constraint solver; f32 sensor windows / observations (as the reference)"})
+    if not args.full:                        # a plain run: the headline alone
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        env.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     steps_view = gmx.env_state_view(env.env_states())["num_action_steps"]
 
     kern_ms = [a.elapsed_time(b) for a, b in ev[:n_drives]]
@@ -668,29 +754,14 @@ def main():
         c1 = None if (args.no_c1 or world > 1) else c1_line(gmx, args.seed)
         c5 = None if (args.no_policy or world > 1) else policy_rollout(gmx, torch, dev, stream, n, max(3, K // 2), args.seed,
                                                         first_env, R if rollout else 0)
-        out = headline(world, n, K, W, elapsed, ep_stats)
-        out["warmup_steps_run"] = max(w_drives, 1) * R
-        out["config"].update({"workload": "C3: set6_synthetic 20 mixed objects, randomised spawn (object drawn per "
-                                   "episode, spawn_into_scene grid search on the device), steady state: envs "
-                                   "staggered over episode steps 1..250 by an untimed pre-roll, benchmark mix "
-                                   "(1 episode in 4: the closed-loop grasp-lift-hold program; otherwise the "
-                                   "scripted grasp mix: close / squeeze / palm / lift + jitter), canonical "
-                                   "sensor/reward "
-                                   "config, device auto-reset at done / 250 steps; driven as gm_rollout launches "
-                                   f"of {R} env-steps (driver actions, env-step, episode-end record and reset "
-                                   "fused per env; bit-identical to the per-step API, tests/test_rollout.py)"
-                                   if rollout else "the per-step API",
-                       "substeps_per_env_step": S,
+        out["config"].update({
                        "B_substep_bytes": B["bytes"], "B_substep_ncon": B["ncon"], "B_substep_nefc": B["nefc"],
                        "measured_contacts": {"mean_ncon": round(float(ncon_m.mean()), 3),
                                              "mean_nefc": round(float(nefc_m.mean()), 3),
                                              "max_ncon": int(ncon_m.max()), "max_nefc": int(nefc_m.max()),
                                              "B_substep_bytes_at_mean_ncon": Bm["bytes"],
                                              "episode_step_spread": [int(steps_view.min()), int(steps_view.max()),
-                                                                     round(float(steps_view.mean()), 1)]},
-                       "model": {"nq": env.model.nq, "nv": env.model.nv, "nbody": env.model.nbody,
-                                 "ngeom": env.model.ngeom, "nM": env.model.nM, "nlock": env.model.nlock},
-                       "dtype_detail": "f64 dynamics, collision and constraint solver; f32 sensor windows / observations (as the reference)"})
+                                                                     round(float(steps_view.mean()), 1)]}})
         out.update({
             "roofline": roof,
             "constraint_solver": solver,

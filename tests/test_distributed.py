@@ -321,6 +321,6 @@ def test_bench_cli_contract():
     out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--help"], capture_output=True, text=True,
                          timeout=120)
     assert out.returncode == 0, out.stderr
-    for opt in ("--gpus", "--steps", "--warmup", "--rollout", "--c2-rollout", "--no-scripted", "--no-random",
-                "--no-c2", "--no-c1", "--no-policy", "--no-cpu", "--no-parity"):
+    for opt in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs", "--rollout", "--c2-rollout",
+                "--no-scripted", "--no-random", "--no-c2", "--no-c1", "--no-policy", "--no-cpu", "--no-parity"):
         assert opt in out.stdout, opt

@@ -10,6 +10,6 @@ timeout -k 10 900 python -u -m pytest "$@" -m gpu -v -s --timeout 300 --timeout-
 tail -2 $OUT/tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 600 python -u $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python -u $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
 cut -c1-600 $OUT/bench.json
 echo "quick ok"

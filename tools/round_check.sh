@@ -11,7 +11,7 @@ if [ "${2:-}" != "skip-tests" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $OUT/smoke.log; exit 1; }
   tail -1 $OUT/smoke.log
 fi
-timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
 cut -c1-400 $OUT/bench.json
 timeout -k 10 300 python -u tools/phase_profile_grasp.py 4096 > $OUT/phase_grasp.txt 2>&1 || { echo "phase profile failed"; tail -5 $OUT/phase_grasp.txt; exit 1; }
 cat $OUT/phase_grasp.txt
