@@ -1,0 +1,137 @@
+// gm_ac.hip -- the batched PPO actor-critic kernels (gm_ac_act / gm_ac_record / gm_ac_finish)
+// and the GAE-lambda scan; network layout, sampling and the one-env form are in gm_ac_net.h
+// (shared with gm_rollout's per-env driver, gm_kernels.hip ac_rollout_driver).
+#pragma once
+#include "gm_ac_net.h"
+
+// One net's forward for a tile of 16 envs (gm_policy_kernel's loop with the net's activation
+// code): observations of envs e0 .. e0 + 15 -> act[cur][env row][output].  copy, when
+// non-NULL, receives the observations ([n_envs][n_obs], the trajectory's obs[k]).
+__device__ __forceinline__ int ga_forward_tile(const float* __restrict__ obs, float* __restrict__ copy, int e0,
+                                               int n_envs, const float* __restrict__ params, const GpNet& P, int code,
+                                               float (*act)[GP_TILE][GA_W], int lane) {
+  const int n_obs = P.width[0];
+  const int k0 = P.kpad[0];
+  __syncthreads();   // the previous net's outputs have been read
+  for (int i = lane; i < GP_TILE * k0; i += 64) {
+    const int r = i / k0, k = i - r * k0;
+    const bool in = e0 + r < n_envs && k < n_obs;
+    const float o = in ? obs[(size_t)(e0 + r) * n_obs + k] : 0.0f;
+    act[0][r][k] = o;
+    if (copy && in) copy[(size_t)(e0 + r) * n_obs + k] = o;
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int l = 0; l < P.n_layers; l++) {
+    const float* __restrict__ W = params + P.woff[l];
+    const float* __restrict__ Bv = params + P.boff[l];
+    const int ksteps = P.kpad[l] >> 2;
+    const bool last = (l == P.n_layers - 1);
+    const int outw = P.width[l + 1];
+    for (int t = 0; t < P.tiles[l]; t++) {
+      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+      const float* Wt = W + (size_t)t * ksteps * 64;
+      for (int s = 0; s < ksteps; s++) {
+        const float a = act[cur][lane & 15][4 * s + (lane >> 4)];
+        const float b = Wt[s * 64 + lane];
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+      }
+      // D fragment: output column j = 16 t + (lane & 15), env row (lane >> 4) * 4 + r
+      const int j = t * 16 + (lane & 15);
+      const float bias = Bv[j];
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        float v = c[r] + bias;
+        if (!last) v = ga_activate(v, code);
+        act[cur ^ 1][(lane >> 4) * 4 + r][j] = (j < outw) ? v : 0.0f;
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  return cur;
+}
+
+// what: 0 gm_ac_act (row k: obs, mu, act, logp, val), 1 gm_ac_record (row k: rew, end, boot),
+// 2 gm_ac_finish (last_val).  One wave per 16 envs.
+__global__ __launch_bounds__(64) void gm_ac_kernel(int what, const float* __restrict__ obs,
+                                                   const GmEnvState* __restrict__ states,
+                                                   const float* __restrict__ rew, const uint8_t* __restrict__ done,
+                                                   int n_envs, long long env_offset, GaArgs A, int k, int max_ep) {
+  __shared__ float act[2][GP_TILE][GA_W];
+  __shared__ float asamp[GP_TILE][GA_MAX_ACT];
+  const int lane = threadIdx.x;
+  const int e0 = blockIdx.x * GP_TILE;
+  const bool mine = lane < GP_TILE && e0 + lane < n_envs;
+  const size_t env = (size_t)(e0 + lane);
+  const size_t row = (size_t)k * (size_t)n_envs + env;
+  const float* cparams = A.params + A.net.critic_off;
+  if (what == 0) {
+    const int n_obs = A.net.actor.width[0];
+    const int na = A.net.actor.width[A.net.actor.n_layers];
+    int cur = ga_forward_tile(obs, A.t_obs + (size_t)k * n_envs * n_obs, e0, n_envs, A.params, A.net.actor,
+                              A.net.act_actor, act, lane);
+    if (mine) {
+      const float* mu = act[cur][lane];
+      A.t_logp[row] = ga_sample(mu, A.params + A.net.log_std_off, na, A.sample, A.noise, A.seed,
+                                A.decision0 + (uint64_t)k, (uint64_t)(env_offset + (long long)env), asamp[lane]);
+      for (int i = 0; i < na; i++) {
+        A.t_act[row * na + i] = asamp[lane][i];
+        if (A.t_mu) A.t_mu[row * na + i] = mu[i];
+      }
+    }
+    cur = ga_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);
+    if (mine) A.t_val[row] = act[cur][lane][0];
+    return;
+  }
+  if (what == 1) {
+    int end = 0;
+    if (mine) end = done[env] ? 1 : (max_ep > 0 && states[env].num_action_steps >= max_ep) ? 2 : 0;
+    float b = 0.0f;
+    if (__ballot(end == 2) != 0ull) {   // (wave-uniform) some env of the tile was truncated
+      const int cur = ga_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);
+      if (end == 2) b = act[cur][lane][0];
+    }
+    if (mine) {
+      A.t_rew[row] = rew[env];
+      A.t_end[row] = (uint8_t)end;
+      A.t_boot[row] = b;
+    }
+    return;
+  }
+  const int cur = ga_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);
+  if (mine) A.t_last_val[env] = act[cur][lane][0];
+}
+
+// GAE-lambda advantages and rewards-to-go over a trajectory buffer (PPOBuffer.finish_trajectory,
+// rl/agents/PolicyGradient.py:355-380, per env and per trajectory segment).  One thread per
+// env, scanning k backwards: every load and store is coalesced across envs.
+//   next_v = end == 1 ? 0 : end == 2 ? boot[k] : (k == K - 1 ? last_val : val[k + 1])
+//   delta  = rew[k] + gamma next_v - val[k]
+//   adv[k] = delta + (end ? 0 : gamma lam adv[k + 1])                       (adv[K] = 0)
+//   ret[k] = rew[k] + gamma (end == 1 ? 0 : end == 2 ? boot[k] : (k == K - 1 ? last_val : ret[k + 1]))
+__global__ __launch_bounds__(64) void gm_ac_gae_kernel(const float* __restrict__ rew, const float* __restrict__ val,
+                                                       const uint8_t* __restrict__ end, const float* __restrict__ boot,
+                                                       const float* __restrict__ last_val, int n_envs, int K,
+                                                       float gamma, float lam, float* __restrict__ adv,
+                                                       float* __restrict__ ret) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env >= n_envs) return;
+  const float lv = last_val[env];
+  float v_next = lv, r_next = lv, a_next = 0.0f;
+  for (int k = K - 1; k >= 0; k--) {
+    const size_t i = (size_t)k * (size_t)n_envs + (size_t)env;
+    const int e = end[i];
+    const float r = rew[i], v = val[i];
+    const float tail = e == 1 ? 0.0f : boot[i];
+    const float nv = e ? tail : v_next;
+    const float delta = r + gamma * nv - v;
+    const float a = e ? delta : delta + gamma * lam * a_next;
+    const float g = r + gamma * (e ? tail : r_next);
+    adv[i] = a;
+    ret[i] = g;
+    v_next = v;
+    r_next = g;
+    a_next = a;
+  }
+}

@@ -1,0 +1,145 @@
+// gm_ac_net.h -- on-device PPO actor-critic (shared by gm_ac.hip's batched kernels and the
+// rollout driver in gm_kernels.hip).
+//
+// Reference: rl/agents/PolicyGradient.py:449-552 MLPGaussianActor / MLPCritic /
+// MLPActorCriticPG.step and :1348-1386 Agent_PPO.select_action:
+//   mu = mu_net(obs)          mlp([n_obs, *hidden, n_actions], Tanh), identity output layer
+//   std = exp(log_std)        log_std a free vector of n_actions
+//   a = mu + std z            z ~ N(0, 1)
+//   logp = sum_i ( -(a_i - mu_i)^2 / (2 std_i^2) - log_std_i - 0.5 log(2 pi) )
+//   v = v_net(obs)            mlp([n_obs, *hidden, 1], Tanh)
+// and, with exploration noise > 0, a uniform draw in [-noise, noise) per action added to a
+// AFTER logp is taken.  The stored action is the noisy, unclipped one; the env clips it.
+//
+// Arithmetic and layout are the DQN network's (gm_policy_net.h): f32, v_mfma_f32_16x16x4_f32,
+// each net packed by gm_policy_pack's B-fragment layout.  One parameter blob holds
+//   [actor net | critic net | log_std[n_actions]]
+// (GaNet::critic_off / log_std_off, in floats).  The hidden activation is a per-network code
+// (GaNet::act_*), so GpNet and the DQN's ReLU code are untouched.
+//
+// Random draws.  Counter-based, keyed by (seed, global env id, decision index, action index),
+// so they depend neither on sharding nor on which wave runs the env:
+//   h   = gp_mix(seed ^ gp_mix(gid * 0x100000001B3 + decision))      (the eps-greedy key)
+//   c_j = gp_mix(h + 3 i + j)   for action i, j = 1, 2, 3            (64-bit wrap-around)
+//   u1 = ((c_1 >> 40) + 1) / 2^24   in (0, 1]      u2 = (c_2 >> 40) / 2^24   in [0, 1)
+//   z  = sqrt(-2 log(u1)) cos(2 pi u2)                                (Box-Muller)
+//   u3 = (c_3 >> 40) / 2^24,  noise draw = noise (2 u3 - 1)           in [-noise, noise)
+// gmx/ppo.py normal_draws / noise_draws mirror this in float64.
+#pragma once
+#include "gm_policy_net.h"
+
+#define GP_ACT_RELU 0
+#define GP_ACT_TANH 1
+#define GA_MAX_ACT 40                     // n_actions the sampler's LDS rows hold
+#define GA_W (GP_MAX_WIDTH + 4)            // one activation row
+#define GA_ONE_FLOATS (2 * GA_W + GA_MAX_ACT)   // the one-env form's LDS scratch, in floats
+
+struct GaNet {
+  GpNet actor, critic;
+  int act_actor, act_critic;    // hidden activation codes (GP_ACT_*)
+  long long critic_off;         // float offset of the critic's packed net in the blob
+  long long log_std_off;        // and of log_std
+};
+
+// one rollout launch's (or per-step call's) arguments; the trajectory pointers are indexed
+// [k][env] with n_envs envs per step (include/gripper_mi355x.h gm_ac_traj)
+struct GaArgs {
+  GaNet net;
+  const float* params;
+  float* t_obs; float* t_act; float* t_logp; float* t_val; float* t_rew; uint8_t* t_end; float* t_boot;
+  float* t_last_val; float* t_mu;
+  int sample;                   // 0: a = mu
+  float noise;
+  uint64_t seed, decision0;     // env-step k of the launch draws with decision0 + k
+};
+
+__device__ __forceinline__ float ga_activate(float v, int code) {
+  return code == GP_ACT_TANH ? tanhf(v) : fmaxf(v, 0.0f);
+}
+
+// Sampling and log-probability for ONE env on ONE lane (the batched kernel and the rollout
+// driver both call this, never a copy of it, so a and logp are bit for bit the same for the
+// same mu).  mu, a: n_act floats; returns logp.
+__device__ __noinline__ float ga_sample(const float* mu, const float* __restrict__ log_std, int n_act, int sample,
+                                        float noise, uint64_t seed, uint64_t decision, uint64_t gid, float* a) {
+  const uint64_t h = gp_mix(seed ^ gp_mix(gid * 0x100000001B3ull + decision));
+  float logp = 0.0f;
+  for (int i = 0; i < n_act; i++) {
+    const float ls = log_std[i];
+    const float sd = expf(ls);
+    const float m = mu[i];
+    float ai = m;
+    if (sample) {
+      const uint64_t c1 = gp_mix(h + 3ull * (uint64_t)i + 1ull), c2 = gp_mix(h + 3ull * (uint64_t)i + 2ull);
+      const float u1 = (float)((double)((c1 >> 40) + 1ull) * (1.0 / 16777216.0));
+      const float u2 = (float)((double)(c2 >> 40) * (1.0 / 16777216.0));
+      const float z = sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+      ai = m + sd * z;
+    }
+    const float d = ai - m;
+    logp += -(d * d) / (2.0f * (sd * sd)) - ls - 0.91893853320467274178f;
+    if (noise > 0.0f) {
+      const uint64_t c3 = gp_mix(h + 3ull * (uint64_t)i + 3ull);
+      const float u3 = (float)((double)(c3 >> 40) * (1.0 / 16777216.0));
+      ai = ai + noise * (2.0f * u3 - 1.0f);
+    }
+    a[i] = ai;
+  }
+  return logp;
+}
+
+// One net's forward for ONE env on its own wave: gp_select_one's tiles (the env in row 0, zero
+// rows below; MFMA rows are independent, so every output is bit for bit the batched kernel's
+// for the same observation).  obs is read with agent-scope loads (see gp_select_one); copy,
+// when non-NULL, receives the observation as loaded.  act: 2 x GA_W floats of LDS.  Returns
+// the buffer (0 / 1) whose row holds the outputs.
+__device__ __forceinline__ int ga_forward_one(const float* obs, float* copy, const float* __restrict__ params,
+                                              const GpNet& P, int code, float* act, int lane) {
+  const int n_obs = P.width[0];
+  const int k0 = P.kpad[0];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  for (int k = lane; k < k0; k += 64) {
+    const float o = k < n_obs ? __hip_atomic_load(obs + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+    act[k] = o;
+    if (copy && k < n_obs) copy[k] = o;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  int cur = 0;
+  for (int l = 0; l < P.n_layers; l++) {
+    const float* __restrict__ Wl = params + P.woff[l];
+    const float* __restrict__ Bv = params + P.boff[l];
+    const int ksteps = P.kpad[l] >> 2;
+    const bool last = (l == P.n_layers - 1);
+    const int outw = P.width[l + 1];
+    const float* src = act + cur * GA_W;
+    float* dst = act + (cur ^ 1) * GA_W;
+    for (int t = 0; t < P.tiles[l]; t++) {
+      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+      const float* Wt = Wl + (size_t)t * ksteps * 64;
+      for (int s = 0; s < ksteps; s++) {
+        const float a = (lane & 15) == 0 ? src[4 * s + (lane >> 4)] : 0.0f;
+        const float b = Wt[s * 64 + lane];
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+      }
+      const int j = t * 16 + (lane & 15);
+      if (lane < 16) {
+        float v = c[0] + Bv[j];
+        if (!last) v = ga_activate(v, code);
+        dst[j] = (j < outw) ? v : 0.0f;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    cur ^= 1;
+  }
+  return cur;
+}
+
+// The critic alone for one env (gm_ac_record's bootstrap value, gm_ac_finish's last value).
+__device__ __forceinline__ float ga_value_one(const float* obs, const GaArgs& A, float* act, int lane) {
+  const int cur = ga_forward_one(obs, nullptr, A.params + A.net.critic_off, A.net.critic, A.net.act_critic, act, lane);
+  return act[cur * GA_W];
+}

@@ -20,6 +20,7 @@
 
 #include "gm_kernels.hip"
 #include "gm_policy.hip"
+#include "gm_ac.hip"
 
 // calibration translation unit (gm_calib.hip)
 hipError_t gm_cal_launch_step(int n_seg, int n_envs, hipStream_t st, GmEnvState* states, const gm_model* m,
@@ -122,6 +123,8 @@ struct RolloutArgs {
   GpNet pnet{};
   const float* peps = nullptr;
   uint64_t pdecision = 0;
+  // act_mode 5 (gm_ac_rollout): the device copy of the launch's actor-critic arguments
+  const GaArgs* ac = nullptr;
 };
 hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, const RolloutArgs* roll = nullptr) {
   // the full env-step (mode 0) runs in cost-sorted order and records each env's cost
@@ -155,6 +158,7 @@ hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, 
     q.peps = roll->peps;
     q.pseed = roll->act_seed;
     q.pdecision = roll->pdecision;
+    q.ac = roll->ac;
   }
   if (chunked) grid = c->chunk_grid;
   // the env-step proper (not the settle, a diagnostic substep or a profiled step) on DUO
@@ -1466,6 +1470,228 @@ int gm_policy_read(gm_policy* p, int32_t* actions, float* q) {
     HIPCHK(c, hipMemcpyAsync(q, p->d_q, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions,
                              hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- on-device PPO actor-critic
+struct gm_ac {
+  gm_ctx* ctx = nullptr;
+  GaNet net{};
+  int64_t total = 0;           // packed floats
+  int64_t n_raw = 0;           // floats of the caller's (state_dict order) parameters
+  std::vector<int32_t> asz, csz;
+  float* d_params = nullptr;
+  GaArgs* d_args = nullptr;    // gm_ac_rollout's launch arguments
+};
+
+static_assert(GA_MAX_ACT >= GM_ACTION_CODE_COUNT, "the sampler's rows hold every action");
+
+static int64_t ac_layout(const int32_t* asz, int na, const int32_t* csz, int nc, GaNet* net, int64_t* n_raw) {
+  GaNet N{};
+  const int64_t ta = policy_layout(asz, na, &N.actor);
+  const int64_t tc = policy_layout(csz, nc, &N.critic);
+  if (ta < 0 || tc < 0) return -1;
+  N.act_actor = N.act_critic = GP_ACT_TANH;
+  N.critic_off = ta;
+  N.log_std_off = ta + tc;
+  if (net) *net = N;
+  if (n_raw) {
+    int64_t r = 0;
+    for (int l = 0; l + 1 < na; l++) r += (int64_t)asz[l + 1] * asz[l] + asz[l + 1];
+    for (int l = 0; l + 1 < nc; l++) r += (int64_t)csz[l + 1] * csz[l] + csz[l + 1];
+    *n_raw = r + asz[na - 1];
+  }
+  return ta + tc + asz[na - 1];
+}
+
+// the device-side view of a caller's trajectory buffer
+static void ac_fill(GaArgs& A, const gm_ac* p, const gm_ac_traj* t, int sample, float noise, uint64_t seed,
+                    uint64_t decision0) {
+  A.net = p->net;
+  A.params = p->d_params;
+  A.t_obs = t->obs; A.t_act = t->act; A.t_logp = t->logp; A.t_val = t->val; A.t_rew = t->rew; A.t_end = t->end;
+  A.t_boot = t->boot; A.t_last_val = t->last_val; A.t_mu = t->mu;
+  A.sample = sample;
+  A.noise = noise;
+  A.seed = seed;
+  A.decision0 = decision0;
+}
+static bool ac_traj_ok(const gm_ac_traj* t) {
+  return t && t->capacity >= 1 && t->obs && t->act && t->logp && t->val && t->rew && t->end && t->boot && t->last_val;
+}
+static int ac_launch(gm_ac* p, int what, const GaArgs& A, int k, int max_ep) {
+  gm_ctx* c = p->ctx;
+  const int blocks = (c->n_envs + GP_TILE - 1) / GP_TILE;
+  hipLaunchKernelGGL(gm_ac_kernel, dim3(blocks), dim3(64), 0, c->stream, what, c->d_obs, c->d_state, c->d_rew,
+                     c->d_done, c->n_envs, (long long)c->env_offset, A, k, max_ep);
+  HIPCHK(c, hipGetLastError());
+  return GM_OK;
+}
+// host bytes -> device, owned by the stream before the call returns: through the context's
+// pinned staging buffer (stage_ev: its previous copy has left it), or copy and wait
+static int ac_upload(gm_ctx* c, void* dst, const void* src, size_t bytes) {
+  if (bytes <= c->stage_bytes) {
+    HIPCHK(c, hipEventSynchronize(c->stage_ev));
+    std::memcpy(c->h_stage, src, bytes);
+    HIPCHK(c, hipMemcpyAsync(dst, c->h_stage, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->stage_ev, c->stream));
+  } else {
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return GM_OK;
+}
+
+extern "C" {
+
+int64_t gm_ac_pack(const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes, int n_critic,
+                   const float* params, float* out, int64_t* off2) {
+  GaNet N;
+  if (!actor_sizes || !critic_sizes || n_actor < 2 || n_critic < 2) return -1;
+  const int64_t total = ac_layout(actor_sizes, n_actor, critic_sizes, n_critic, &N, nullptr);
+  if (total < 0) return total;
+  if (off2) { off2[0] = N.critic_off; off2[1] = N.log_std_off; }
+  if (!out) return total;
+  if (!params) return GM_E_ARG;
+  const float* src = params;
+  gm_policy_pack(actor_sizes, n_actor, src, out);
+  for (int l = 0; l + 1 < n_actor; l++) src += (size_t)actor_sizes[l + 1] * actor_sizes[l] + actor_sizes[l + 1];
+  gm_policy_pack(critic_sizes, n_critic, src, out + N.critic_off);
+  for (int l = 0; l + 1 < n_critic; l++) src += (size_t)critic_sizes[l + 1] * critic_sizes[l] + critic_sizes[l + 1];
+  std::memcpy(out + N.log_std_off, src, sizeof(float) * (size_t)actor_sizes[n_actor - 1]);
+  return total;
+}
+
+int gm_ac_create(gm_ctx* c, const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes, int n_critic,
+                 const float* params, gm_ac** out) {
+  if (!c || !actor_sizes || !critic_sizes || !params || !out || n_actor < 2 || n_critic < 2) return GM_E_ARG;
+  GaNet N;
+  int64_t n_raw = 0;
+  const int64_t total = ac_layout(actor_sizes, n_actor, critic_sizes, n_critic, &N, &n_raw);
+  if (total < 0) return fail(c, GM_E_ARG, "gm_ac_create: <= 8 layers of width 1..256 expected");
+  if (!c->cfg.s.continous_actions)
+    return fail(c, GM_E_ARG, "gm_ac_create: the Gaussian actor needs continuous actions (continous_actions != 0)");
+  if (N.actor.width[0] != c->cfg.n_obs || N.actor.width[N.actor.n_layers] != c->cfg.n_actions)
+    return fail(c, GM_E_ARG, "gm_ac_create: the actor must map n_obs (" + std::to_string(c->cfg.n_obs) +
+                                 ") to n_actions (" + std::to_string(c->cfg.n_actions) + ")");
+  if (N.critic.width[0] != c->cfg.n_obs || N.critic.width[N.critic.n_layers] != 1)
+    return fail(c, GM_E_ARG, "gm_ac_create: the critic must map n_obs (" + std::to_string(c->cfg.n_obs) + ") to 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  gm_ac* p = new gm_ac;
+  p->ctx = c;
+  p->net = N;
+  p->total = total;
+  p->n_raw = n_raw;
+  p->asz.assign(actor_sizes, actor_sizes + n_actor);
+  p->csz.assign(critic_sizes, critic_sizes + n_critic);
+  hipError_t e = hipMalloc(&p->d_params, sizeof(float) * (size_t)total);
+  if (e == hipSuccess) e = hipMalloc(&p->d_args, sizeof(GaArgs));
+  if (e != hipSuccess) {
+    gm_ac_destroy(p);
+    return fail(c, GM_E_HIP, std::string("gm_ac_create: ") + hipGetErrorString(e));
+  }
+  const int rc = gm_ac_set_params(p, params);
+  if (rc != GM_OK) { gm_ac_destroy(p); return rc; }
+  *out = p;
+  return GM_OK;
+}
+
+void gm_ac_destroy(gm_ac* p) {
+  if (!p) return;
+  if (p->ctx) {
+    (void)hipSetDevice(p->ctx->device);
+    (void)hipStreamSynchronize(p->ctx->stream);
+  }
+  (void)hipFree(p->d_params);
+  (void)hipFree(p->d_args);
+  delete p;
+}
+
+int gm_ac_set_params(gm_ac* p, const float* params) {
+  if (!p || !p->ctx || !params) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<float> packed((size_t)p->total);
+  gm_ac_pack(p->asz.data(), (int)p->asz.size(), p->csz.data(), (int)p->csz.size(), params, packed.data(), nullptr);
+  return ac_upload(c, p->d_params, packed.data(), sizeof(float) * (size_t)p->total);
+}
+
+int gm_ac_act(gm_ac* p, const gm_ac_traj* traj, int k, int sample, float noise, uint64_t seed, uint64_t decision) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  if (!ac_traj_ok(traj) || k < 0 || k >= traj->capacity || !(noise >= 0.0f))
+    return fail(c, GM_E_ARG, "gm_ac_act: incomplete trajectory buffer, k outside its capacity or negative noise");
+  HIPCHK(c, hipSetDevice(c->device));
+  GaArgs A{};
+  // (the kernel draws with decision0 + k)
+  ac_fill(A, p, traj, sample, noise, seed, decision - (uint64_t)k);
+  const int rc = ac_launch(p, 0, A, k, 0);
+  if (rc != GM_OK) return rc;
+  return gm_set_action(c, traj->act + (size_t)k * c->n_envs * c->cfg.n_actions, 1);
+}
+
+int gm_ac_record(gm_ac* p, const gm_ac_traj* traj, int k, int max_episode_steps) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  if (!ac_traj_ok(traj) || k < 0 || k >= traj->capacity)
+    return fail(c, GM_E_ARG, "gm_ac_record: incomplete trajectory buffer or k outside its capacity");
+  HIPCHK(c, hipSetDevice(c->device));
+  GaArgs A{};
+  ac_fill(A, p, traj, 0, 0.0f, 0, 0);
+  return ac_launch(p, 1, A, k, max_episode_steps);
+}
+
+int gm_ac_finish(gm_ac* p, const gm_ac_traj* traj, int k_last) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  if (!ac_traj_ok(traj) || k_last < 0 || k_last >= traj->capacity)
+    return fail(c, GM_E_ARG, "gm_ac_finish: incomplete trajectory buffer or k_last outside its capacity");
+  HIPCHK(c, hipSetDevice(c->device));
+  GaArgs A{};
+  ac_fill(A, p, traj, 0, 0.0f, 0, 0);
+  return ac_launch(p, 2, A, k_last, 0);
+}
+
+int gm_ac_rollout(gm_ac* p, const gm_ac_traj* traj, int n_steps, int sample, float noise, uint64_t seed,
+                  uint64_t decision0, int max_episode_steps, gm_episode_end* records) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  if (!ac_traj_ok(traj) || n_steps < 1 || n_steps > traj->capacity || !(noise >= 0.0f))
+    return fail(c, GM_E_ARG, "gm_ac_rollout: incomplete trajectory buffer, n_steps outside its capacity or negative noise");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->chunk > 0 && c->chunk_grid > 0) {
+    GaArgs A{};
+    ac_fill(A, p, traj, sample, noise, seed, decision0);
+    const int rc = ac_upload(c, p->d_args, &A, sizeof(GaArgs));
+    if (rc != GM_OK) return rc;
+    RolloutArgs ra{n_steps, 5, seed, 0.0f, max_episode_steps, records};
+    ra.ac = p->d_args;
+    return rollout_launch(c, ra);
+  }
+  // the one-shot kernel (GM_CHUNK_SUBSTEPS=0): the per-step sequence it fuses
+  for (int k = 0; k < n_steps; k++) {
+    int rc = gm_ac_act(p, traj, k, sample, noise, seed, decision0 + (uint64_t)k);
+    if (rc == GM_OK) rc = gm_step(c);
+    if (rc == GM_OK) rc = gm_ac_record(p, traj, k, max_episode_steps);
+    if (rc == GM_OK) rc = gm_autoreset_episodes(c, max_episode_steps, nullptr, 1, nullptr,
+                                                records ? records + (size_t)k * c->n_envs : nullptr);
+    if (rc != GM_OK) return rc;
+  }
+  return gm_ac_finish(p, traj, n_steps - 1);
+}
+
+int gm_ac_gae(gm_ctx* c, const gm_ac_traj* traj, int n_steps, float gamma, float lam, float* adv, float* ret) {
+  if (!c) return GM_E_ARG;
+  if (!traj || !traj->rew || !traj->val || !traj->end || !traj->boot || !traj->last_val || !adv || !ret ||
+      n_steps < 1 || n_steps > traj->capacity)
+    return fail(c, GM_E_ARG, "gm_ac_gae: incomplete trajectory buffer or n_steps outside its capacity");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
+  hipLaunchKernelGGL(gm_ac_gae_kernel, dim3(blocks), dim3(threads), 0, c->stream, traj->rew, traj->val, traj->end,
+                     traj->boot, traj->last_val, c->n_envs, n_steps, gamma, lam, adv, ret);
+  HIPCHK(c, hipGetLastError());
   return GM_OK;
 }
 

@@ -25,6 +25,7 @@
 #include "gm_state.h"
 #include "gm_math.h"
 #include "gm_policy_net.h"
+#include "gm_ac_net.h"
 
 #define NT 64
 // Phase boundary inside one env's physics.  Every kernel that runs the substep is launched
@@ -2598,7 +2599,9 @@ struct GmChunkQ {
   // (gm_scripted_actions / gm_random_actions) -> set_continous_action -> action_step + obs /
   // done / reward -> gm_autoreset_episodes' episode-end record and reset
   int steps;
-  int act_mode;              // 0 scripted grasp mix, 1 uniform random, -1 none
+  int act_mode;              // -1 none (gm_step); 0 scripted grasp mix, 1 uniform random, 3 grasp program,
+                             // 4 program / scripted mix (gm_rollout); 2 DQN policy (gm_policy_rollout);
+                             // 5 PPO actor-critic (gm_ac_rollout)
   uint64_t act_seed;
   float jitter;
   int max_ep;                // truncation (num_action_steps >= max_ep), <= 0 off
@@ -2617,6 +2620,9 @@ struct GmChunkQ {
   GpNet pnet;
   const float* peps;         // [steps] exploration threshold per env-step of the launch
   uint64_t pseed, pdecision; // the policy's seed and the first env-step's decision index
+  // act_mode 5: the PPO actor-critic samples each env-step's continuous action on the env's own
+  // wave and fills the trajectory buffer (gm_ac_rollout; ac_rollout_driver)
+  const GaArgs* ac;          // device copy of the launch's arguments
 };
 __device__ __forceinline__ void st_agent(uint64_t* p, uint64_t v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2692,6 +2698,63 @@ __device__ __noinline__ void driver_actions(GmEnvHot& s, RingRef R, const gm_mod
     f[i] = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
   }
   for (int i = 0; i < na; i++) set_action_one(s, m, C, i, f[i]);
+}
+
+// act_mode 5 (gm_ac_rollout): the actor-critic's part of one env's env-step on the env's own
+// wave, kept out of the substep loop's instruction stream (called between env-steps only).
+//   phase 0, before the env-step: gm_ac_act on this env alone -- observation, mu, the sampled
+//     action, logp and V(obs) into trajectory row k, then lane 0 applies the clipped actions in
+//     order (gm_action_kernel's loop);
+//   phase 1, after the epilogue and before the auto-reset: gm_ac_record -- reward, end code
+//     and, for a truncated env only, the critic on the post-step observation;
+//   phase 2, after the env's last env-step: gm_ac_finish -- the critic on the observation left
+//     in the buffer (the reset one if the env was reset).
+// scratch: GA_ONE_FLOATS floats of LDS (the dynamics union, dead between env-steps).
+__device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restrict__ Ap, const float* obs, int env,
+                                               int n_envs, int k, int max_ep, int64_t gid, float* scratch,
+                                               GmEnvHot& s, const gm_model* __restrict__ m,
+                                               const gm_config* __restrict__ C, int lane) {
+  const GaArgs& A = *Ap;
+  const size_t row = (size_t)k * (size_t)n_envs + (size_t)env;
+  if (phase == 0) {
+    const int n_obs = A.net.actor.width[0];
+    const int na = A.net.actor.width[A.net.actor.n_layers];
+    const int cur = ga_forward_one(obs, A.t_obs + row * n_obs, A.params, A.net.actor, A.net.act_actor, scratch, lane);
+    float* a = scratch + 2 * GA_W;
+    if (lane == 0) {
+      const float* mu = scratch + cur * GA_W;
+      A.t_logp[row] = ga_sample(mu, A.params + A.net.log_std_off, na, A.sample, A.noise, A.seed,
+                                A.decision0 + (uint64_t)k, (uint64_t)gid, a);
+      for (int i = 0; i < na; i++) {
+        A.t_act[row * na + i] = a[i];
+        if (A.t_mu) A.t_mu[row * na + i] = mu[i];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const float v = ga_value_one(obs, A, scratch, lane);
+    if (lane == 0) {
+      A.t_val[row] = v;
+      for (int i = 0; i < na; i++) {
+        float f = a[i];
+        if (f < -1.0f) f = -1.0f; else if (f > 1.0f) f = 1.0f;
+        set_action_one(s, m, C, i, f);
+      }
+    }
+  } else if (phase == 1) {
+    const int end = __builtin_amdgcn_readfirstlane(s.done ? 1 : (max_ep > 0 && s.num_action_steps >= max_ep) ? 2 : 0);
+    float b = 0.0f;
+    if (end == 2) b = ga_value_one(obs, A, scratch, lane);
+    if (lane == 0) {
+      A.t_rew[row] = s.reward;
+      A.t_end[row] = (uint8_t)end;
+      A.t_boot[row] = b;
+    }
+  } else {
+    const float v = ga_value_one(obs, A, scratch, lane);
+    if (lane == 0) A.t_last_val[env] = v;
+  }
 }
 
 // the persistent loop of gm_step_kernel's chunked mode (a mode of the one kernel, not a
@@ -2890,6 +2953,11 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
             set_action_one(S.s, m, C, a, 0.0f);
             S.stp_fixed = 0;
           }
+        } else if (q.act_mode == 5) {
+          static_assert(sizeof(S.st) >= sizeof(float) * GA_ONE_FLOATS, "actor-critic activations fit the union");
+          ac_rollout_driver(0, q.ac, obs + (size_t)env * C->n_obs, env, n_envs, cr.step_idx, q.max_ep,
+                            q.sr.env_offset + env, reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
+          if (lane == 0) S.stp_fixed = 0;
         } else if (lane == 0) {
           driver_actions(S.s, g->ring, m, C, q.act_mode, q.act_seed, q.jitter, q.sr.env_offset + env);
           S.stp_fixed = 0;
@@ -2926,6 +2994,9 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
           e.pad[0] = e.pad[1] = e.pad[2] = 0;
           q.rec[(size_t)cr.step_idx * n + env] = e;
         }
+        if (q.act_mode == 5)
+          ac_rollout_driver(1, q.ac, obs + (size_t)env * C->n_obs, env, n_envs, cr.step_idx, q.max_ep,
+                            q.sr.env_offset + env, reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
         if (r) {
           GM_ENV_SYNC();   // lane 0's epilogue writes (RNG, counters) before every lane reads them
           const GmResetKeep keep{S.s.rng, S.s.old_x, S.s.old_y, S.s.old_z, S.s.episode + 1, S.s.newton_caps};
@@ -2940,7 +3011,13 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
       }
       cr.steps_left -= 1;
       cr.step_idx += 1;
-      if (cr.steps_left <= 0) { finished = true; break; }
+      if (cr.steps_left <= 0) {
+        if (q.act_mode == 5)
+          ac_rollout_driver(2, q.ac, obs + (size_t)env * C->n_obs, env, n_envs, cr.step_idx, q.max_ep,
+                            q.sr.env_offset + env, reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
+        finished = true;
+        break;
+      }
       cr.sub_done = 0;
       cr.yielded = 0;
       GM_ENV_SYNC();

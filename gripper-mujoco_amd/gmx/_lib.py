@@ -282,6 +282,15 @@ def _declare(lib):
         "gm_policy_act": (i32, [vp, C.c_float, C.c_uint64, C.c_uint64]),
         "gm_policy_read": (i32, [vp, i32p, f32p]),
         "gm_policy_rollout": (i32, [vp, i32, f32p, C.c_uint64, C.c_uint64, i32, vp]),
+        "gm_ac_create": (i32, [vp, i32p, i32, i32p, i32, f32p, C.POINTER(vp)]),
+        "gm_ac_destroy": (None, [vp]),
+        "gm_ac_set_params": (i32, [vp, f32p]),
+        "gm_ac_pack": (C.c_int64, [i32p, i32, i32p, i32, f32p, f32p, C.POINTER(C.c_int64)]),
+        "gm_ac_act": (i32, [vp, vp, i32, i32, C.c_float, C.c_uint64, C.c_uint64]),
+        "gm_ac_record": (i32, [vp, vp, i32, i32]),
+        "gm_ac_finish": (i32, [vp, vp, i32]),
+        "gm_ac_rollout": (i32, [vp, vp, i32, i32, C.c_float, C.c_uint64, C.c_uint64, i32, vp]),
+        "gm_ac_gae": (i32, [vp, vp, i32, C.c_float, C.c_float, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -1,0 +1,283 @@
+"""On-device PPO data collection for the batched env: a Gaussian actor and a critic evaluated
+on the device, a device trajectory buffer and the GAE-lambda scan.
+
+Mirrors the reference's policy-gradient rollout side:
+  - MLPActorCriticPG.step (rl/agents/PolicyGradient.py:522-528): mu = mu_net(obs), a = mu +
+    exp(log_std) z, logp = Normal(mu, std).log_prob(a).sum(-1), v = v_net(obs); both nets are
+    mlp([...], Tanh) with an identity output layer (:47-55, 449-500);
+  - Agent_PPO.select_action (:1348-1388): uniform exploration noise added after logp;
+  - PPOBuffer (:301-409): finish_trajectory's GAE-lambda advantages and rewards-to-go, get()'s
+    advantage normalisation.
+There is no trainer here: the learner is the user's torch code, which reads
+TrajectoryBuffer.get() and hands new weights back with DeviceActorCritic.set_params().
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from ._lib import load_library
+
+DEFAULT_HIDDEN = (64, 64)          # MLPActorCriticPG's default hidden_sizes
+LOG_STD_INIT = -0.5                # MLPGaussianActor
+
+_M64 = (1 << 64) - 1
+
+
+def _mix(z):
+    """gp_mix (csrc/gm_policy_net.h): splitmix64's finaliser on uint64 arrays."""
+    z = np.asarray(z, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def _counters(seed, gids, decision, n_actions, j):
+    """c_j of csrc/gm_ac_net.h for every (env, action): [len(gids), n_actions] uint64."""
+    gids = np.atleast_1d(np.asarray(gids, dtype=np.uint64))
+    with np.errstate(over="ignore"):
+        h = _mix(np.uint64(int(seed) & _M64) ^ _mix(gids * np.uint64(0x100000001B3) + np.uint64(int(decision) & _M64)))
+        i = np.arange(n_actions, dtype=np.uint64)
+        return _mix(h[:, None] + np.uint64(3) * i[None, :] + np.uint64(j))
+
+
+def normal_draws(seed, gids, decision, n_actions) -> np.ndarray:
+    """The device sampler's standard normal draws z (float64) for global env ids `gids` at one
+    decision index: Box-Muller on two 24-bit uniforms, the first in (0, 1]."""
+    u1 = ((_counters(seed, gids, decision, n_actions, 1) >> np.uint64(40)).astype(np.float64) + 1.0) / 16777216.0
+    u2 = (_counters(seed, gids, decision, n_actions, 2) >> np.uint64(40)).astype(np.float64) / 16777216.0
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def noise_draws(seed, gids, decision, n_actions, noise: float) -> np.ndarray:
+    """The device's uniform exploration noise in [-noise, noise) (float64)."""
+    u3 = (_counters(seed, gids, decision, n_actions, 3) >> np.uint64(40)).astype(np.float64) / 16777216.0
+    return float(noise) * (2.0 * u3 - 1.0)
+
+
+def _linear_init(rng, sizes):
+    parts = []
+    for i in range(len(sizes) - 1):
+        fan_in, fan_out = sizes[i], sizes[i + 1]
+        bound = 1.0 / math.sqrt(fan_in)
+        parts.append(rng.uniform(-bound, bound, size=(fan_out, fan_in)).astype(np.float32).ravel())
+        parts.append(rng.uniform(-bound, bound, size=fan_out).astype(np.float32))
+    return parts
+
+
+def init_params(actor_sizes, critic_sizes, seed: int = 0) -> np.ndarray:
+    """nn.Linear's default init for both nets and log_std = -0.5, flattened: the actor's W0
+    [out x in], b0, W1, b1, ..., the critic's likewise, then log_std."""
+    rng = np.random.default_rng(seed)
+    parts = _linear_init(rng, actor_sizes) + _linear_init(rng, critic_sizes)
+    parts.append(np.full(actor_sizes[-1], LOG_STD_INIT, dtype=np.float32))
+    return np.concatenate(parts).astype(np.float32)
+
+
+def _np(t):
+    return np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32)
+
+
+def params_from_state_dict(state_dict):
+    """(actor_sizes, critic_sizes, flat params) from an MLPActorCriticPG state dict: pi.log_std,
+    pi.mu_net.{0,2,..}.weight / .bias, vf.v_net.{0,2,..}.weight / .bias."""
+    def net(prefix):
+        ws = sorted((k for k in state_dict if k.startswith(prefix) and k.endswith(".weight")),
+                    key=lambda k: int(k[len(prefix):].split(".")[0]))
+        if not ws:
+            raise KeyError(f"no {prefix}*.weight in the state dict")
+        sizes = [int(state_dict[ws[0]].shape[1])]
+        parts = []
+        for k in ws:
+            w = _np(state_dict[k])
+            sizes.append(int(w.shape[0]))
+            parts += [w.ravel(), _np(state_dict[k[:-len("weight")] + "bias"]).ravel()]
+        return sizes, parts
+    asz, ap = net("pi.mu_net.")
+    csz, cp = net("vf.v_net.")
+    log_std = _np(state_dict["pi.log_std"]).ravel()
+    return asz, csz, np.concatenate(ap + cp + [log_std]).astype(np.float32)
+
+
+def n_params(actor_sizes, critic_sizes) -> int:
+    """Floats of the flat parameters (init_params' order) for these layer sizes."""
+    return (sum(s[i + 1] * s[i] + s[i + 1] for s in (actor_sizes, critic_sizes) for i in range(len(s) - 1))
+            + actor_sizes[-1])
+
+
+def pack(actor_sizes, critic_sizes, params):
+    """(packed blob, critic offset, log_std offset): the device layout (gm_ac_pack; testable
+    without a GPU).  Raises ValueError for unsupported sizes or a wrong parameter count."""
+    lib = load_library()
+    a = np.ascontiguousarray(actor_sizes, dtype=np.int32)
+    c = np.ascontiguousarray(critic_sizes, dtype=np.int32)
+    pr = np.ascontiguousarray(params, dtype=np.float32).ravel()
+    i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    off = (C.c_int64 * 2)()
+    n = lib.gm_ac_pack(a.ctypes.data_as(i32p), len(a), c.ctypes.data_as(i32p), len(c), pr.ctypes.data_as(f32p), None, off)
+    if n < 0:
+        raise ValueError("unsupported network sizes")
+    want = n_params([int(x) for x in a], [int(x) for x in c])
+    if pr.size != want:
+        raise ValueError(f"{want} parameters expected for these sizes, got {pr.size}")
+    out = np.zeros(n, dtype=np.float32)
+    lib.gm_ac_pack(a.ctypes.data_as(i32p), len(a), c.ctypes.data_as(i32p), len(c), pr.ctypes.data_as(f32p),
+                   out.ctypes.data_as(f32p), off)
+    return out, int(off[0]), int(off[1])
+
+
+class AcTraj(C.Structure):
+    """gm_ac_traj (include/gripper_mi355x.h)."""
+    _fields_ = [("capacity", C.c_int32), ("pad", C.c_int32), ("obs", C.c_void_p), ("act", C.c_void_p),
+                ("logp", C.c_void_p), ("val", C.c_void_p), ("rew", C.c_void_p), ("end", C.c_void_p),
+                ("boot", C.c_void_p), ("last_val", C.c_void_p), ("mu", C.c_void_p)]
+
+
+class TrajectoryBuffer:
+    """K env-steps of every env, as torch tensors on the env's device in gm_ac_traj's layout
+    (time-major: all envs of one env-step are contiguous)."""
+
+    def __init__(self, env, K: int, keep_mu: bool = True):
+        import torch
+        self.env = env
+        self.K = int(K)
+        n, dev = env.n_envs, f"cuda:{env.device}"
+        f = dict(dtype=torch.float32, device=dev)
+        self.obs = torch.zeros((self.K, n, env.n_obs), **f)
+        self.act = torch.zeros((self.K, n, env.n_actions), **f)
+        self.logp = torch.zeros((self.K, n), **f)
+        self.val = torch.zeros((self.K, n), **f)
+        self.rew = torch.zeros((self.K, n), **f)
+        self.end = torch.zeros((self.K, n), dtype=torch.uint8, device=dev)
+        self.boot = torch.zeros((self.K, n), **f)
+        self.last_val = torch.zeros((n,), **f)
+        self.mu = torch.zeros((self.K, n, env.n_actions), **f) if keep_mu else None
+        self.adv = torch.zeros((self.K, n), **f)
+        self.ret = torch.zeros((self.K, n), **f)
+        torch.cuda.synchronize(dev)    # the zero fills, before the env's own stream writes
+
+    def struct(self, k0: int = 0) -> AcTraj:
+        """The gm_ac_traj of rows k0 .. K - 1 (row k0 is the struct's row 0)."""
+        t = AcTraj()
+        t.capacity = self.K - k0
+        for name in ("obs", "act", "logp", "val", "rew", "end", "boot"):
+            setattr(t, name, getattr(self, name)[k0:].data_ptr())
+        t.last_val = self.last_val.data_ptr()
+        t.mu = self.mu[k0:].data_ptr() if self.mu is not None else None
+        return t
+
+    def gae(self, gamma: float, lam: float, n_steps: int | None = None):
+        """gm_ac_gae over the first n_steps rows: (adv, ret) device tensors [n_steps, n_envs]."""
+        import torch
+        k = self.K if n_steps is None else int(n_steps)
+        t = self.struct()
+        torch.cuda.synchronize(self.adv.device)     # torch-side writes to the buffers (tests)
+        rc = self.env.lib.gm_ac_gae(self.env.ctx, C.byref(t), k, C.c_float(gamma), C.c_float(lam),
+                                    C.c_void_p(self.adv.data_ptr()), C.c_void_p(self.ret.data_ptr()))
+        if rc != 0:
+            raise RuntimeError(self.env.lib.gm_last_error(self.env.ctx).decode() or f"gm_ac_gae failed ({rc})")
+        torch.cuda.synchronize(self.adv.device)     # the env's stream, before torch reads the results
+        return self.adv[:k], self.ret[:k]
+
+    def get(self, gamma: float = 0.99, lam: float = 0.97, n_steps: int | None = None) -> dict:
+        """PPOBuffer.get (PolicyGradient.py:384-409): obs, act, ret, adv, logp flattened to
+        [n_steps * n_envs, ...], the advantages normalised with torch.std_mean (unbiased)."""
+        import torch
+        adv, ret = self.gae(gamma, lam, n_steps)
+        k = adv.shape[0]
+        std, mean = torch.std_mean(adv)
+        return dict(obs=self.obs[:k].reshape(-1, self.obs.shape[-1]), act=self.act[:k].reshape(-1, self.act.shape[-1]),
+                    ret=ret.reshape(-1), adv=((adv - mean) / std).reshape(-1), logp=self.logp[:k].reshape(-1))
+
+
+class DeviceActorCritic:
+    """An MLPActorCriticPG (Gaussian actor, critic) bound to a BatchedGripperEnv with
+    continuous actions."""
+
+    def __init__(self, env, hidden=DEFAULT_HIDDEN, params=None, seed: int = 0, hidden_v=None,
+                 actor_sizes=None, critic_sizes=None):
+        self.env = env
+        self.lib = env.lib
+        hv = hidden if hidden_v is None else hidden_v
+        self.actor_sizes = [int(x) for x in (actor_sizes or [env.n_obs, *hidden, env.n_actions])]
+        self.critic_sizes = [int(x) for x in (critic_sizes or [env.n_obs, *hv, 1])]
+        self.params = (init_params(self.actor_sizes, self.critic_sizes, seed) if params is None
+                       else np.ascontiguousarray(params, np.float32).copy())
+        self._p = C.c_void_p()
+        if min(self.actor_sizes + self.critic_sizes) < 1 or len(self.actor_sizes) < 2 or len(self.critic_sizes) < 2:
+            raise ValueError("layer sizes must be positive, with at least an input and an output")
+        want = n_params(self.actor_sizes, self.critic_sizes)
+        if self.params.ndim != 1 or self.params.size != want:      # (the library reads exactly this many)
+            raise ValueError(f"{want} parameters expected for these sizes, got {self.params.size}")
+        a = np.ascontiguousarray(self.actor_sizes, dtype=np.int32)
+        c = np.ascontiguousarray(self.critic_sizes, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        rc = self.lib.gm_ac_create(env.ctx, a.ctypes.data_as(i32p), len(a), c.ctypes.data_as(i32p), len(c),
+                                   self.params.ctypes.data_as(C.POINTER(C.c_float)), C.byref(self._p))
+        if rc != 0:
+            raise RuntimeError(self.lib.gm_last_error(env.ctx).decode() or f"gm_ac_create failed ({rc})")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(self.lib.gm_last_error(self.env.ctx).decode() or f"{what} failed ({rc})")
+
+    def set_params(self, params):
+        """New weights after a learner update (flat, init_params' order, or a state dict)."""
+        if isinstance(params, dict):
+            asz, csz, params = params_from_state_dict(params)
+            if asz != self.actor_sizes or csz != self.critic_sizes:
+                raise ValueError("state dict does not match the network sizes")
+        p = np.ascontiguousarray(params, np.float32)
+        if p.size != self.params.size:
+            raise ValueError(f"{self.params.size} parameters expected, got {p.size}")
+        self.params = p.copy()
+        self._check(self.lib.gm_ac_set_params(self._p, self.params.ctypes.data_as(C.POINTER(C.c_float))), "gm_ac_set_params")
+
+    def act(self, traj: TrajectoryBuffer, k: int, sample: bool = True, noise: float = 0.0, seed: int = 0,
+            decision: int = 0):
+        """select_action for every env from its current observation into row k, applied on the device."""
+        t = traj.struct()
+        self._check(self.lib.gm_ac_act(self._p, C.byref(t), int(k), int(bool(sample)), C.c_float(noise),
+                                       C.c_uint64(seed), C.c_uint64(decision)), "gm_ac_act")
+
+    def record(self, traj: TrajectoryBuffer, k: int, max_episode_steps: int | None = None):
+        """After the env-step, before the auto-reset: reward, end code and bootstrap value of row k."""
+        mx = self.env.max_episode_steps if max_episode_steps is None else max_episode_steps
+        t = traj.struct()
+        self._check(self.lib.gm_ac_record(self._p, C.byref(t), int(k), int(mx)), "gm_ac_record")
+
+    def finish(self, traj: TrajectoryBuffer, k_last: int | None = None):
+        t = traj.struct()
+        self._check(self.lib.gm_ac_finish(self._p, C.byref(t), int(traj.K - 1 if k_last is None else k_last)),
+                    "gm_ac_finish")
+
+    def rollout(self, traj: TrajectoryBuffer, n_steps: int | None = None, sample: bool = True, noise: float = 0.0,
+                seed: int = 0, decision0: int = 0, max_episode_steps: int | None = None,
+                records_dev_ptr: int | None = None, k0: int = 0):
+        """gm_ac_rollout into rows k0 .. k0 + n_steps - 1: act(decision0 + i) -> env step -> record
+        -> auto-reset for each, then finish, fused into one persistent launch (bit for bit the
+        per-step sequence).  records_dev_ptr: device [n_steps x n_envs] gm_episode_end records."""
+        n = traj.K - k0 if n_steps is None else int(n_steps)
+        mx = self.env.max_episode_steps if max_episode_steps is None else max_episode_steps
+        t = traj.struct(k0)
+        self._check(self.lib.gm_ac_rollout(self._p, C.byref(t), n, int(bool(sample)), C.c_float(noise), C.c_uint64(seed),
+                                           C.c_uint64(decision0), int(mx), C.c_void_p(records_dev_ptr or 0)),
+                    "gm_ac_rollout")
+
+    def gae(self, traj: TrajectoryBuffer, gamma: float = 0.99, lam: float = 0.97, n_steps: int | None = None):
+        return traj.gae(gamma, lam, n_steps)
+
+    def close(self):
+        if self._p:
+            self.lib.gm_ac_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -594,7 +594,9 @@ int  gm_autoreset_episodes(gm_ctx* ctx, int max_episode_steps, const gm_spawn* s
  * env-step's (the reset observation for envs reset at its end), as after the per-step calls. */
 typedef struct gm_rollout_params {
   int32_t  action_mode;        /* 0: scripted grasp mix, 1: uniform random, 3: grasp program,
-                                  4: program in 1 episode of 4, scripted mix otherwise */
+                                  4: program in 1 episode of 4, scripted mix otherwise
+                                  (2 and 5 are the launch's internal codes for gm_policy_rollout
+                                  and gm_ac_rollout; gm_rollout rejects them) */
   int32_t  max_episode_steps;  /* MjEnv truncation; <= 0 disables it */
   uint64_t seed;
   float    jitter;             /* scripted mode only */
@@ -697,6 +699,81 @@ int  gm_policy_read(gm_policy* p, int32_t* actions, float* q);
  * launch (they are under GM_CHUNK_SUBSTEPS=0, which runs the per-step sequence). */
 int  gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed, uint64_t decision0,
                        int max_episode_steps, gm_episode_end* records);
+
+/* ---- on-device PPO actor-critic, trajectory buffer and GAE ----
+ * MLPActorCriticPG.step (rl/agents/PolicyGradient.py:522-528) and Agent_PPO.select_action
+ * (:1348-1386) on every env's current observation:
+ *   mu = mu_net(obs) (MLPGaussianActor, :449-471: Linear+Tanh hidden layers, identity output),
+ *   std = exp(log_std), a = mu + std z with z ~ N(0, 1),
+ *   logp = sum_i ( -(a_i - mu_i)^2 / (2 std_i^2) - log_std_i - 0.5 log(2 pi) )  (Normal.log_prob
+ *   summed over the action axis), v = v_net(obs) (MLPCritic, :473-487),
+ * then, with noise > 0, uniform noise in [-noise, noise) per action added to a after logp is
+ * taken (select_action's exploration noise).  The actions go to the envs on the device through
+ * the continuous-action path, which clips to [-1, 1] (MjEnv._set_action, rl/env/MjEnv.py:591-594:
+ * set_action_one once per action index, in order); the buffer keeps the unclipped ones.
+ * f32, the DQN network's MFMA, packing and limits (<= 8 layers, widths <= 256).  Draws are
+ * counter-based per (seed, global env id, decision, action index) -- csrc/gm_ac_net.h has the
+ * construction, gmx/ppo.py normal_draws / noise_draws its host mirror -- so results do not
+ * depend on sharding.
+ *
+ * The trajectory buffer is the caller's device memory (PPOBuffer, PolicyGradient.py:301-409),
+ * time-major so that all envs of one env-step are contiguous. */
+typedef struct gm_ac_traj {
+  int32_t capacity;   /* env-steps K the arrays hold */
+  int32_t pad;
+  float*   obs;       /* [K][n_envs][n_obs]   observation the action was chosen from */
+  float*   act;       /* [K][n_envs][n_actions] action sent to the env (noisy, unclipped) */
+  float*   logp;      /* [K][n_envs] */
+  float*   val;       /* [K][n_envs]  V(obs[k]) */
+  float*   rew;       /* [K][n_envs]  reward of env-step k */
+  uint8_t* end;       /* [K][n_envs]  0 episode continues, 1 terminal (done), 2 truncated only */
+  float*   boot;      /* [K][n_envs]  V(observation after env-step k) where end == 2, else 0 */
+  float*   last_val;  /* [n_envs]     V(observation after the last recorded env-step) */
+  float*   mu;        /* [K][n_envs][n_actions], may be NULL (diagnostics / tests) */
+} gm_ac_traj;
+typedef struct gm_ac gm_ac;
+/* actor_sizes: [n_obs, hidden..., n_actions]; critic_sizes: [n_obs, hidden..., 1]; params (host,
+ * f32): the actor's W0 [sizes[1] x sizes[0]] row-major, b0, W1, b1, ..., then the critic's in
+ * the same order, then log_std [n_actions].  Needs continous_actions != 0 (the mirror of
+ * gm_policy_create's check); GM_E_ARG with a gm_last_error message for a network that does
+ * not map n_obs to n_actions / to 1 or has unsupported sizes. */
+int  gm_ac_create(gm_ctx* ctx, const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes,
+                  int n_critic, const float* params, gm_ac** out);
+void gm_ac_destroy(gm_ac* p);
+/* New weights after a learner update (Agent_PPO.update_step's result): same layout as
+ * gm_ac_create's params; copied before the call returns. */
+int  gm_ac_set_params(gm_ac* p, const float* params);
+/* Host-side repack into the device layout: [actor | critic] each in gm_policy_pack's layout,
+ * then log_std.  Returns the packed float count (negative for unsupported sizes), writes `out`
+ * when non-NULL.  off2 (may be NULL): the critic's and log_std's float offsets. */
+int64_t gm_ac_pack(const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes, int n_critic,
+                   const float* params, float* out, int64_t* off2);
+/* select_action for every env from its current observation: fills obs[k], act[k], logp[k],
+ * val[k] (and mu[k]) and applies the actions.  sample = 0: a = mu (evaluation; logp is mu's). */
+int  gm_ac_act(gm_ac* p, const gm_ac_traj* traj, int k, int sample, float noise, uint64_t seed,
+               uint64_t decision);
+/* After gm_step and BEFORE the auto-reset: rew[k], end[k] (1 done, else 2 when
+ * max_episode_steps > 0 and the episode reached it, else 0) and boot[k] -- the critic on the
+ * post-step observation where end == 2 (PPOBuffer.finish_trajectory's last_val of a cut
+ * trajectory, Agent_PPO's truncation bootstrap), 0 elsewhere. */
+int  gm_ac_record(gm_ac* p, const gm_ac_traj* traj, int k, int max_episode_steps);
+/* last_val from the current observations, after env-step k_last's auto-reset. */
+int  gm_ac_finish(gm_ac* p, const gm_ac_traj* traj, int k_last);
+/* The fused form: for k = 0 .. n_steps - 1
+ *   gm_ac_act(k, decision0 + k) -> gm_step -> gm_ac_record(k, max_episode_steps)
+ *   -> gm_autoreset_episodes(max_episode_steps, spawn = NULL, records + k * n_envs)
+ * then gm_ac_finish(n_steps - 1), as ONE persistent launch of gm_rollout's kind: each env's own
+ * wave runs actor and critic (the batched kernels' MFMA tiles with the env in row 0) between
+ * its env-steps.  Every result -- state, observations, records and the whole buffer -- equals
+ * the per-step sequence's bit for bit.  Under GM_CHUNK_SUBSTEPS=0 it runs that sequence.
+ * records: device [n_steps x n_envs] or NULL. */
+int  gm_ac_rollout(gm_ac* p, const gm_ac_traj* traj, int n_steps, int sample, float noise, uint64_t seed,
+                   uint64_t decision0, int max_episode_steps, gm_episode_end* records);
+/* GAE-lambda advantages and rewards-to-go (PPOBuffer.finish_trajectory, PolicyGradient.py:355-380)
+ * per env and trajectory segment over the first n_steps rows of traj (reads rew, val, end,
+ * boot, last_val only); adv, ret: device [n_steps][n_envs]. */
+int  gm_ac_gae(gm_ctx* ctx, const gm_ac_traj* traj, int n_steps, float gamma, float lam, float* adv,
+               float* ret);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Resource usage of the gm_step_kernel instantiations in a compiled gm_capi object, read from
+the gfx950 code object's metadata (no GPU needed): VGPRs, SGPRs, LDS bytes, scratch bytes per
+lane and code size of each kernel, plus the code size of named device functions.
+
+Compare two trees ("PPO actor-critic rollout"):
+  python -c "import __graft_entry__ as g; g.build()"        # in each tree
+  python tools/step_kernel_resources.py --label parent --label this --out profiles/ac_rollout_step_kernel_resources.json \\
+         <parent tree>/gripper-mujoco_amd/lib/obj/gm_capi.hip.o gripper-mujoco_amd/lib/obj/gm_capi.hip.o
+The script exits 1 when the last object's LDS or scratch exceeds the first's for any kernel."""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
+TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+FUNCS = ("ac_rollout_driver", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel")
+
+
+def tool(name, *args):
+    return subprocess.run([os.path.join(LLVM, name), *args], check=True, capture_output=True, text=True).stdout
+
+
+def usage(obj):
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, "fat"), os.path.join(d, "co")
+        tool("llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj)
+        tool("clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={fat}", f"--output={co}")
+        notes = tool("llvm-readelf", "--notes", co)
+        syms = tool("llvm-readelf", "-sW", co)
+    size = {}
+    for line in syms.splitlines():
+        f = line.split()
+        if len(f) >= 8 and f[3] == "FUNC":
+            size[f[7]] = int(f[2])
+    kernels = {}
+    for blk in notes.split("- .agpr_count")[1:]:
+        def g(key):
+            return re.search(r"\." + key + r":\s+(\S+)", blk).group(1)
+        name = g("name")
+        if "gm_step_kernel" not in name:
+            continue
+        m = re.search(r"gm_step_kernelILi(\d+)ELb(\d)ELb(\d)E", name)
+        short = f"CL={m.group(1)} CAL={m.group(2)} DUO={m.group(3)}" if m else name
+        kernels[short] = dict(vgpr=int(g("vgpr_count")), sgpr=int(g("sgpr_count")),
+                              lds_bytes=int(g("group_segment_fixed_size")),
+                              scratch_bytes_per_lane=int(g("private_segment_fixed_size")), code_bytes=size.get(name))
+    funcs = {f: n for s, n in size.items() for f in FUNCS if f in s}
+    return dict(kernels=kernels, functions=funcs)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--label", action="append", default=[])
+    ap.add_argument("--out")
+    ap.add_argument("objects", nargs="+")
+    a = ap.parse_intermixed_args()
+    labels = a.label + [os.path.basename(o) for o in a.objects[len(a.label):]]
+    res = {lab: usage(obj) for lab, obj in zip(labels, a.objects)}
+    grew = []
+    if len(labels) > 1:
+        first, last = res[labels[0]]["kernels"], res[labels[-1]]["kernels"]
+        for k in sorted(first):
+            for field in ("lds_bytes", "scratch_bytes_per_lane"):
+                if k in last and last[k][field] > first[k][field]:
+                    grew.append(f"{k} {field} {first[k][field]} -> {last[k][field]}")
+        res["lds_or_scratch_grew"] = grew
+    text = json.dumps(res, indent=1, sort_keys=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+    return 1 if grew else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
