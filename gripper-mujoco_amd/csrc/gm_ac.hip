@@ -1,56 +1,9 @@
 // gm_ac.hip -- the batched PPO actor-critic kernels (gm_ac_act / gm_ac_record / gm_ac_finish)
-// and the GAE-lambda scan; network layout, sampling and the one-env form are in gm_ac_net.h
-// (shared with gm_rollout's per-env driver, gm_kernels.hip ac_rollout_driver).
+// and the GAE-lambda scan.  The forward is gm_policy_net.h's gp_forward_tile with each net's
+// activation code; sampling is gm_ac_net.h's ga_sample (both shared with gm_rollout's per-env
+// driver, gm_kernels.hip ac_rollout_driver).
 #pragma once
 #include "gm_ac_net.h"
-
-// One net's forward for a tile of 16 envs (gm_policy_kernel's loop with the net's activation
-// code): observations of envs e0 .. e0 + 15 -> act[cur][env row][output].  copy, when
-// non-NULL, receives the observations ([n_envs][n_obs], the trajectory's obs[k]).
-__device__ __forceinline__ int ga_forward_tile(const float* __restrict__ obs, float* __restrict__ copy, int e0,
-                                               int n_envs, const float* __restrict__ params, const GpNet& P, int code,
-                                               float (*act)[GP_TILE][GA_W], int lane) {
-  const int n_obs = P.width[0];
-  const int k0 = P.kpad[0];
-  __syncthreads();   // the previous net's outputs have been read
-  for (int i = lane; i < GP_TILE * k0; i += 64) {
-    const int r = i / k0, k = i - r * k0;
-    const bool in = e0 + r < n_envs && k < n_obs;
-    const float o = in ? obs[(size_t)(e0 + r) * n_obs + k] : 0.0f;
-    act[0][r][k] = o;
-    if (copy && in) copy[(size_t)(e0 + r) * n_obs + k] = o;
-  }
-  __syncthreads();
-  int cur = 0;
-  for (int l = 0; l < P.n_layers; l++) {
-    const float* __restrict__ W = params + P.woff[l];
-    const float* __restrict__ Bv = params + P.boff[l];
-    const int ksteps = P.kpad[l] >> 2;
-    const bool last = (l == P.n_layers - 1);
-    const int outw = P.width[l + 1];
-    for (int t = 0; t < P.tiles[l]; t++) {
-      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
-      const float* Wt = W + (size_t)t * ksteps * 64;
-      for (int s = 0; s < ksteps; s++) {
-        const float a = act[cur][lane & 15][4 * s + (lane >> 4)];
-        const float b = Wt[s * 64 + lane];
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-      }
-      // D fragment: output column j = 16 t + (lane & 15), env row (lane >> 4) * 4 + r
-      const int j = t * 16 + (lane & 15);
-      const float bias = Bv[j];
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        float v = c[r] + bias;
-        if (!last) v = ga_activate(v, code);
-        act[cur ^ 1][(lane >> 4) * 4 + r][j] = (j < outw) ? v : 0.0f;
-      }
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  return cur;
-}
 
 // what: 0 gm_ac_act (row k: obs, mu, act, logp, val), 1 gm_ac_record (row k: rew, end, boot),
 // 2 gm_ac_finish (last_val).  One wave per 16 envs.
@@ -58,7 +11,7 @@ __global__ __launch_bounds__(64) void gm_ac_kernel(int what, const float* __rest
                                                    const GmEnvState* __restrict__ states,
                                                    const float* __restrict__ rew, const uint8_t* __restrict__ done,
                                                    int n_envs, long long env_offset, GaArgs A, int k, int max_ep) {
-  __shared__ float act[2][GP_TILE][GA_W];
+  __shared__ float act[2][GP_TILE][GP_ROW];
   __shared__ float asamp[GP_TILE][GA_MAX_ACT];
   const int lane = threadIdx.x;
   const int e0 = blockIdx.x * GP_TILE;
@@ -69,7 +22,7 @@ __global__ __launch_bounds__(64) void gm_ac_kernel(int what, const float* __rest
   if (what == 0) {
     const int n_obs = A.net.actor.width[0];
     const int na = A.net.actor.width[A.net.actor.n_layers];
-    int cur = ga_forward_tile(obs, A.t_obs + (size_t)k * n_envs * n_obs, e0, n_envs, A.params, A.net.actor,
+    int cur = gp_forward_tile(obs, A.t_obs + (size_t)k * n_envs * n_obs, e0, n_envs, A.params, A.net.actor,
                               A.net.act_actor, act, lane);
     if (mine) {
       const float* mu = act[cur][lane];
@@ -80,7 +33,7 @@ __global__ __launch_bounds__(64) void gm_ac_kernel(int what, const float* __rest
         if (A.t_mu) A.t_mu[row * na + i] = mu[i];
       }
     }
-    cur = ga_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);
+    cur = gp_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);
     if (mine) A.t_val[row] = act[cur][lane][0];
     return;
   }
@@ -89,7 +42,7 @@ __global__ __launch_bounds__(64) void gm_ac_kernel(int what, const float* __rest
     if (mine) end = done[env] ? 1 : (max_ep > 0 && states[env].num_action_steps >= max_ep) ? 2 : 0;
     float b = 0.0f;
     if (__ballot(end == 2) != 0ull) {   // (wave-uniform) some env of the tile was truncated
-      const int cur = ga_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);
+      const int cur = gp_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);
       if (end == 2) b = act[cur][lane][0];
     }
     if (mine) {
@@ -99,7 +52,7 @@ __global__ __launch_bounds__(64) void gm_ac_kernel(int what, const float* __rest
     }
     return;
   }
-  const int cur = ga_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);
+  const int cur = gp_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);
   if (mine) A.t_last_val[env] = act[cur][lane][0];
 }
 

@@ -1,5 +1,6 @@
-// gm_ac_net.h -- on-device PPO actor-critic (shared by gm_ac.hip's batched kernels and the
-// rollout driver in gm_kernels.hip).
+// gm_ac_net.h -- on-device PPO actor-critic: GaNet / GaArgs, the sampler ga_sample and the
+// one-env critic ga_value_one (shared by gm_ac.hip's batched kernels and the rollout driver
+// in gm_kernels.hip).
 //
 // Reference: rl/agents/PolicyGradient.py:449-552 MLPGaussianActor / MLPCritic /
 // MLPActorCriticPG.step and :1348-1386 Agent_PPO.select_action:
@@ -14,8 +15,9 @@
 // Arithmetic and layout are the DQN network's (gm_policy_net.h): f32, v_mfma_f32_16x16x4_f32,
 // each net packed by gm_policy_pack's B-fragment layout.  One parameter blob holds
 //   [actor net | critic net | log_std[n_actions]]
-// (GaNet::critic_off / log_std_off, in floats).  The hidden activation is a per-network code
-// (GaNet::act_*), so GpNet and the DQN's ReLU code are untouched.
+// (GaNet::critic_off / log_std_off, in floats).  The forward itself is gm_policy_net.h's
+// (gp_forward_tile in gm_ac_kernel, gp_forward_one in the rollout driver), called with each
+// net's hidden activation code (GaNet::act_*); the DQN passes GP_ACT_RELU as a constant.
 //
 // Random draws.  Counter-based, keyed by (seed, global env id, decision index, action index),
 // so they depend neither on sharding nor on which wave runs the env:
@@ -28,11 +30,8 @@
 #pragma once
 #include "gm_policy_net.h"
 
-#define GP_ACT_RELU 0
-#define GP_ACT_TANH 1
 #define GA_MAX_ACT 40                     // n_actions the sampler's LDS rows hold
-#define GA_W (GP_MAX_WIDTH + 4)            // one activation row
-#define GA_ONE_FLOATS (2 * GA_W + GA_MAX_ACT)   // the one-env form's LDS scratch, in floats
+#define GA_ONE_FLOATS (2 * GP_ROW + GA_MAX_ACT)   // the one-env driver's LDS scratch, in floats
 
 struct GaNet {
   GpNet actor, critic;
@@ -52,10 +51,6 @@ struct GaArgs {
   float noise;
   uint64_t seed, decision0;     // env-step k of the launch draws with decision0 + k
 };
-
-__device__ __forceinline__ float ga_activate(float v, int code) {
-  return code == GP_ACT_TANH ? tanhf(v) : fmaxf(v, 0.0f);
-}
 
 // Sampling and log-probability for ONE env on ONE lane (the batched kernel and the rollout
 // driver both call this, never a copy of it, so a and logp are bit for bit the same for the
@@ -88,58 +83,8 @@ __device__ __noinline__ float ga_sample(const float* mu, const float* __restrict
   return logp;
 }
 
-// One net's forward for ONE env on its own wave: gp_select_one's tiles (the env in row 0, zero
-// rows below; MFMA rows are independent, so every output is bit for bit the batched kernel's
-// for the same observation).  obs is read with agent-scope loads (see gp_select_one); copy,
-// when non-NULL, receives the observation as loaded.  act: 2 x GA_W floats of LDS.  Returns
-// the buffer (0 / 1) whose row holds the outputs.
-__device__ __forceinline__ int ga_forward_one(const float* obs, float* copy, const float* __restrict__ params,
-                                              const GpNet& P, int code, float* act, int lane) {
-  const int n_obs = P.width[0];
-  const int k0 = P.kpad[0];
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  for (int k = lane; k < k0; k += 64) {
-    const float o = k < n_obs ? __hip_atomic_load(obs + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-    act[k] = o;
-    if (copy && k < n_obs) copy[k] = o;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  int cur = 0;
-  for (int l = 0; l < P.n_layers; l++) {
-    const float* __restrict__ Wl = params + P.woff[l];
-    const float* __restrict__ Bv = params + P.boff[l];
-    const int ksteps = P.kpad[l] >> 2;
-    const bool last = (l == P.n_layers - 1);
-    const int outw = P.width[l + 1];
-    const float* src = act + cur * GA_W;
-    float* dst = act + (cur ^ 1) * GA_W;
-    for (int t = 0; t < P.tiles[l]; t++) {
-      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
-      const float* Wt = Wl + (size_t)t * ksteps * 64;
-      for (int s = 0; s < ksteps; s++) {
-        const float a = (lane & 15) == 0 ? src[4 * s + (lane >> 4)] : 0.0f;
-        const float b = Wt[s * 64 + lane];
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-      }
-      const int j = t * 16 + (lane & 15);
-      if (lane < 16) {
-        float v = c[0] + Bv[j];
-        if (!last) v = ga_activate(v, code);
-        dst[j] = (j < outw) ? v : 0.0f;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    cur ^= 1;
-  }
-  return cur;
-}
-
 // The critic alone for one env (gm_ac_record's bootstrap value, gm_ac_finish's last value).
 __device__ __forceinline__ float ga_value_one(const float* obs, const GaArgs& A, float* act, int lane) {
-  const int cur = ga_forward_one(obs, nullptr, A.params + A.net.critic_off, A.net.critic, A.net.act_critic, act, lane);
-  return act[cur * GA_W];
+  const int cur = gp_forward_one(obs, nullptr, A.params + A.net.critic_off, A.net.critic, A.net.act_critic, act, lane);
+  return act[cur * GP_ROW];
 }

@@ -103,6 +103,21 @@ int fail(gm_ctx* c, int code, const std::string& msg) {
       return fail(ctx, GM_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));    \
   } while (0)
 
+// host bytes -> device, owned by the stream before the call returns: through the context's
+// pinned staging buffer (stage_ev: its previous copy has left it), or copy and wait
+static int stage_upload(gm_ctx* c, void* dst, const void* src, size_t bytes) {
+  if (bytes <= c->stage_bytes) {
+    HIPCHK(c, hipEventSynchronize(c->stage_ev));
+    std::memcpy(c->h_stage, src, bytes);
+    HIPCHK(c, hipMemcpyAsync(dst, c->h_stage, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->stage_ev, c->stream));
+  } else {
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return GM_OK;
+}
+
 bool nseg_supported(int n) {
   switch (n) {
 #define X(N) case N:
@@ -629,11 +644,8 @@ int gm_set_action(gm_ctx* c, const float* actions, int on_device) {
   HIPCHK(c, hipSetDevice(c->device));
   const float* da = actions;
   if (!on_device) {
-    const size_t bytes = sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions;
-    HIPCHK(c, hipEventSynchronize(c->stage_ev));   // the last staging copy has left the buffer
-    std::memcpy(c->h_stage, actions, bytes);
-    HIPCHK(c, hipMemcpyAsync(c->d_act, c->h_stage, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->stage_ev, c->stream));
+    const int rc = stage_upload(c, c->d_act, actions, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions);
+    if (rc != GM_OK) return rc;
     da = c->d_act;
   }
   int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
@@ -648,11 +660,8 @@ int gm_set_discrete_action(gm_ctx* c, const int32_t* actions, int on_device) {
   HIPCHK(c, hipSetDevice(c->device));
   const int32_t* da = actions;
   if (!on_device) {
-    const size_t bytes = sizeof(int32_t) * (size_t)c->n_envs;
-    HIPCHK(c, hipEventSynchronize(c->stage_ev));
-    std::memcpy(c->h_stage, actions, bytes);
-    HIPCHK(c, hipMemcpyAsync(c->d_dact, c->h_stage, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->stage_ev, c->stream));
+    const int rc = stage_upload(c, c->d_dact, actions, sizeof(int32_t) * (size_t)c->n_envs);
+    if (rc != GM_OK) return rc;
     da = c->d_dact;
   }
   int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
@@ -1378,23 +1387,30 @@ int gm_policy_create(gm_ctx* c, const int32_t* sizes, int n_sizes, const float* 
     return fail(c, GM_E_ARG, "gm_policy_create: the DQN policy needs discrete actions (continous_actions = 0)");
   std::vector<float> packed((size_t)total);
   gm_policy_pack(sizes, n_sizes, params, packed.data());
+  HIPCHK(c, hipSetDevice(c->device));
   gm_policy* p = new gm_policy;
   p->ctx = c;
   p->net = P;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMalloc(&p->d_params, sizeof(float) * (size_t)total));
-  HIPCHK(c, hipMalloc(&p->d_actions, sizeof(int32_t) * (size_t)c->n_envs));
-  HIPCHK(c, hipMalloc(&p->d_q, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions));
-  HIPCHK(c, hipMemcpyAsync(p->d_params, packed.data(), sizeof(float) * (size_t)total, hipMemcpyHostToDevice,
-                           c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hipError_t e = hipMalloc(&p->d_params, sizeof(float) * (size_t)total);
+  if (e == hipSuccess) e = hipMalloc(&p->d_actions, sizeof(int32_t) * (size_t)c->n_envs);
+  if (e == hipSuccess) e = hipMalloc(&p->d_q, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(p->d_params, packed.data(), sizeof(float) * (size_t)total, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    gm_policy_destroy(p);
+    return fail(c, GM_E_HIP, std::string("gm_policy_create: ") + hipGetErrorString(e));
+  }
   *out = p;
   return GM_OK;
 }
 
 void gm_policy_destroy(gm_policy* p) {
   if (!p) return;
-  if (p->ctx) (void)hipSetDevice(p->ctx->device);
+  if (p->ctx) {
+    (void)hipSetDevice(p->ctx->device);
+    (void)hipStreamSynchronize(p->ctx->stream);   // the stream may still read d_params / d_eps
+  }
   (void)hipFree(p->d_params);
   (void)hipFree(p->d_actions);
   (void)hipFree(p->d_q);
@@ -1428,19 +1444,9 @@ int gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed
       HIPCHK(c, hipMalloc(&p->d_eps, sizeof(float) * (size_t)n_steps));
       p->eps_cap = n_steps;
     }
-    // eps is the caller's (pageable) array: stage it through the ctx's pinned buffer so the
-    // copy owns its bytes before the call returns (stage_ev: the previous staging copy has
-    // left the buffer), or copy and wait when it does not fit
-    const size_t eb = sizeof(float) * (size_t)n_steps;
-    if (eb <= c->stage_bytes) {
-      HIPCHK(c, hipEventSynchronize(c->stage_ev));
-      std::memcpy(c->h_stage, eps, eb);
-      HIPCHK(c, hipMemcpyAsync(p->d_eps, c->h_stage, eb, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipEventRecord(c->stage_ev, c->stream));
-    } else {
-      HIPCHK(c, hipMemcpyAsync(p->d_eps, eps, eb, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    // eps is the caller's (pageable) array: the copy owns its bytes before the call returns
+    const int rc = stage_upload(c, p->d_eps, eps, sizeof(float) * (size_t)n_steps);
+    if (rc != GM_OK) return rc;
     RolloutArgs ra{n_steps, 2, seed, 0.0f, max_episode_steps, records};
     ra.pparams = p->d_params;
     ra.pnet = p->net;
@@ -1529,20 +1535,6 @@ static int ac_launch(gm_ac* p, int what, const GaArgs& A, int k, int max_ep) {
   HIPCHK(c, hipGetLastError());
   return GM_OK;
 }
-// host bytes -> device, owned by the stream before the call returns: through the context's
-// pinned staging buffer (stage_ev: its previous copy has left it), or copy and wait
-static int ac_upload(gm_ctx* c, void* dst, const void* src, size_t bytes) {
-  if (bytes <= c->stage_bytes) {
-    HIPCHK(c, hipEventSynchronize(c->stage_ev));
-    std::memcpy(c->h_stage, src, bytes);
-    HIPCHK(c, hipMemcpyAsync(dst, c->h_stage, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->stage_ev, c->stream));
-  } else {
-    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return GM_OK;
-}
 
 extern "C" {
 
@@ -1615,7 +1607,7 @@ int gm_ac_set_params(gm_ac* p, const float* params) {
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<float> packed((size_t)p->total);
   gm_ac_pack(p->asz.data(), (int)p->asz.size(), p->csz.data(), (int)p->csz.size(), params, packed.data(), nullptr);
-  return ac_upload(c, p->d_params, packed.data(), sizeof(float) * (size_t)p->total);
+  return stage_upload(c, p->d_params, packed.data(), sizeof(float) * (size_t)p->total);
 }
 
 int gm_ac_act(gm_ac* p, const gm_ac_traj* traj, int k, int sample, float noise, uint64_t seed, uint64_t decision) {
@@ -1664,7 +1656,7 @@ int gm_ac_rollout(gm_ac* p, const gm_ac_traj* traj, int n_steps, int sample, flo
   if (c->chunk > 0 && c->chunk_grid > 0) {
     GaArgs A{};
     ac_fill(A, p, traj, sample, noise, seed, decision0);
-    const int rc = ac_upload(c, p->d_args, &A, sizeof(GaArgs));
+    const int rc = stage_upload(c, p->d_args, &A, sizeof(GaArgs));
     if (rc != GM_OK) return rc;
     RolloutArgs ra{n_steps, 5, seed, 0.0f, max_episode_steps, records};
     ra.ac = p->d_args;

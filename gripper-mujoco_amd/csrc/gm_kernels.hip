@@ -2719,10 +2719,10 @@ __device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restri
   if (phase == 0) {
     const int n_obs = A.net.actor.width[0];
     const int na = A.net.actor.width[A.net.actor.n_layers];
-    const int cur = ga_forward_one(obs, A.t_obs + row * n_obs, A.params, A.net.actor, A.net.act_actor, scratch, lane);
-    float* a = scratch + 2 * GA_W;
+    const int cur = gp_forward_one(obs, A.t_obs + row * n_obs, A.params, A.net.actor, A.net.act_actor, scratch, lane);
+    float* a = scratch + 2 * GP_ROW;
     if (lane == 0) {
-      const float* mu = scratch + cur * GA_W;
+      const float* mu = scratch + cur * GP_ROW;
       A.t_logp[row] = ga_sample(mu, A.params + A.net.log_std_off, na, A.sample, A.noise, A.seed,
                                 A.decision0 + (uint64_t)k, (uint64_t)gid, a);
       for (int i = 0; i < na; i++) {
@@ -2945,7 +2945,7 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
           // gm_policy_act on this env alone: select_action from its current observation,
           // then set_discrete_action (the LDS scratch: the dynamics union, dead between
           // env-steps)
-          static_assert(sizeof(S.st) >= sizeof(float) * 2 * (GP_MAX_WIDTH + 4), "policy activations fit the union");
+          static_assert(sizeof(S.st) >= sizeof(float) * 2 * GP_ROW, "policy activations fit the union");
           const int a = gp_select_one(obs + (size_t)env * C->n_obs, q.pparams, q.pnet, q.peps[cr.step_idx], q.pseed,
                                       q.pdecision + (uint64_t)cr.step_idx, (uint64_t)(q.sr.env_offset + env),
                                       reinterpret_cast<float*>(&S.st), lane);

@@ -1,5 +1,8 @@
-// gm_policy_net.h -- on-device DQN action selection (shared by gm_policy.hip and the rollout driver) for the batched env (SURVEY.md 8f,
-// rank 1: "fused on-device DQN inference").
+// gm_policy_net.h -- the on-device MLP (network layout and the only two MFMA forwards,
+// gp_forward_tile for 16 envs per wave and gp_forward_one for one env on its own wave) and the
+// DQN action selection on top of it ("fused on-device DQN inference").
+// The DQN callers (gm_policy_kernel, gp_select_one) pass GP_ACT_RELU as a constant; the PPO
+// actor-critic (gm_ac_net.h, gm_ac.hip, ac_rollout_driver) passes each net's run-time code.
 //
 // Reference: rl/networks.py:7-41 VariableNetwork.forward (Linear + ReLU per hidden
 // layer, a final Linear, Softmax over dim 1) and rl/agents/DQN.py:184-209
@@ -23,6 +26,9 @@
 #define GP_MAX_LAYERS 8
 #define GP_MAX_WIDTH 256
 #define GP_TILE 16
+#define GP_ROW (GP_MAX_WIDTH + 4)   // floats per activation row in LDS
+#define GP_ACT_RELU 0               // hidden activation codes
+#define GP_ACT_TANH 1
 
 struct GpNet {
   int n_layers;                   // Linear layers
@@ -46,6 +52,10 @@ __device__ __forceinline__ uint64_t gp_mix(uint64_t z) {
   return z ^ (z >> 31);
 }
 
+// the hidden activation; a caller's literal code folds the other branch away
+__device__ __forceinline__ float gp_activate(float v, int code) {
+  return code == GP_ACT_TANH ? tanhf(v) : fmaxf(v, 0.0f);
+}
 
 // softmax over the logits (nn.Softmax(dim=1)), then Agent_DQN.select_action: argmax (first
 // maximum, like torch's max on CPU) or, with probability eps, a uniform random action from
@@ -70,23 +80,76 @@ __device__ __forceinline__ int gp_choose(const float* x, int n_out, float eps, u
   return best;
 }
 
-// select_action for ONE env on its own wave (gm_rollout's policy driver, gm_kernels.hip
-// chunked_env_steps): the batched kernel's MFMA tiles with this env in row 0 and zero rows
-// below it.  MFMA rows are independent, so every logit is bit for bit the batched kernel's
-// for the same observation.  obs: the env's observation (read with agent-scope loads, past
-// this CU's L1: the env-step epilogue or a reset on another CU may have written it); act:
-// 2 x (GP_MAX_WIDTH + 4) floats of LDS scratch.  Returns the action on every lane.
-__device__ __forceinline__ int gp_select_one(const float* obs, const float* __restrict__ params, const GpNet& P,
-                                             float eps, uint64_t seed, uint64_t decision, uint64_t gid, float* act,
-                                             int lane) {
-  constexpr int W = GP_MAX_WIDTH + 4;
+// One net's forward for a tile of 16 envs, one wave per tile (gm_policy_kernel, gm_ac_kernel):
+// observations of envs e0 .. e0 + 15 of obs[n_envs][n_obs] -> act[cur][env row][output]; returns
+// cur.  Hidden layers get gp_activate(code), the last layer none.  copy, when non-NULL, receives
+// the observations as loaded ([n_envs][n_obs]).  The leading barrier lets a second net reuse
+// the rows once every lane has read the first one's outputs.
+__device__ __forceinline__ int gp_forward_tile(const float* __restrict__ obs, float* __restrict__ copy, int e0,
+                                               int n_envs, const float* __restrict__ params, const GpNet& P, int code,
+                                               float (*act)[GP_TILE][GP_ROW], int lane) {
+  const int n_obs = P.width[0];
+  const int k0 = P.kpad[0];
+  __syncthreads();
+  for (int i = lane; i < GP_TILE * k0; i += 64) {
+    const int r = i / k0, k = i - r * k0;
+    const bool in = e0 + r < n_envs && k < n_obs;
+    const float o = in ? obs[(size_t)(e0 + r) * n_obs + k] : 0.0f;
+    act[0][r][k] = o;
+    if (copy && in) copy[(size_t)(e0 + r) * n_obs + k] = o;
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int l = 0; l < P.n_layers; l++) {
+    const float* __restrict__ W = params + P.woff[l];
+    const float* __restrict__ Bv = params + P.boff[l];
+    const int ksteps = P.kpad[l] >> 2;
+    const bool last = (l == P.n_layers - 1);
+    const int outw = P.width[l + 1];
+    for (int t = 0; t < P.tiles[l]; t++) {
+      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+      const float* Wt = W + (size_t)t * ksteps * 64;
+      for (int s = 0; s < ksteps; s++) {
+        const float a = act[cur][lane & 15][4 * s + (lane >> 4)];
+        const float b = Wt[s * 64 + lane];
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+      }
+      // D fragment: output column j = 16 t + (lane & 15), env row (lane >> 4) * 4 + r
+      const int j = t * 16 + (lane & 15);
+      const float bias = Bv[j];
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        float v = c[r] + bias;
+        if (!last) v = gp_activate(v, code);
+        act[cur ^ 1][(lane >> 4) * 4 + r][j] = (j < outw) ? v : 0.0f;
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  return cur;
+}
+
+// The same forward for ONE env on its own wave (gm_rollout's drivers, gm_kernels.hip
+// chunked_env_steps and ac_rollout_driver): the tile form's MFMA tiles with this env in row 0
+// and zero rows below it.  MFMA rows are independent, so every output is bit for bit the tile
+// form's for the same observation.  obs: the env's observation (read with agent-scope loads,
+// past this CU's L1: the env-step epilogue or a reset on another CU may have written it); copy,
+// when non-NULL, receives it as loaded.  act: 2 x GP_ROW floats of LDS scratch; the wave-level
+// fences order its rows (the workgroup may hold a second wave that must not be waited for).
+// Returns the buffer (0 / 1) whose row holds the outputs.
+__device__ __forceinline__ int gp_forward_one(const float* obs, float* copy, const float* __restrict__ params,
+                                              const GpNet& P, int code, float* act, int lane) {
   const int n_obs = P.width[0];
   const int k0 = P.kpad[0];
   // this wave's own stores of the observation (the previous env-step's epilogue or reset,
   // other lanes) have reached L2 before the loads below go there
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  for (int k = lane; k < k0; k += 64)
-    act[k] = k < n_obs ? __hip_atomic_load(obs + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+  for (int k = lane; k < k0; k += 64) {
+    const float o = k < n_obs ? __hip_atomic_load(obs + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
+    act[k] = o;
+    if (copy && k < n_obs) copy[k] = o;
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -97,8 +160,8 @@ __device__ __forceinline__ int gp_select_one(const float* obs, const float* __re
     const int ksteps = P.kpad[l] >> 2;
     const bool last = (l == P.n_layers - 1);
     const int outw = P.width[l + 1];
-    const float* src = act + cur * W;
-    float* dst = act + (cur ^ 1) * W;
+    const float* src = act + cur * GP_ROW;
+    float* dst = act + (cur ^ 1) * GP_ROW;
     for (int t = 0; t < P.tiles[l]; t++) {
       gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
       const float* Wt = Wl + (size_t)t * ksteps * 64;
@@ -111,7 +174,7 @@ __device__ __forceinline__ int gp_select_one(const float* obs, const float* __re
       const int j = t * 16 + (lane & 15);
       if (lane < 16) {
         float v = c[0] + Bv[j];
-        if (!last) v = fmaxf(v, 0.0f);
+        if (!last) v = gp_activate(v, code);
         dst[j] = (j < outw) ? v : 0.0f;
       }
     }
@@ -120,7 +183,17 @@ __device__ __forceinline__ int gp_select_one(const float* obs, const float* __re
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     cur ^= 1;
   }
+  return cur;
+}
+
+// select_action for ONE env on its own wave (gm_rollout's policy driver, gm_kernels.hip
+// chunked_env_steps): the ReLU forward, then lane 0 chooses.  act: 2 x GP_ROW floats of LDS
+// scratch.  Returns the action on every lane.
+__device__ __forceinline__ int gp_select_one(const float* obs, const float* __restrict__ params, const GpNet& P,
+                                             float eps, uint64_t seed, uint64_t decision, uint64_t gid, float* act,
+                                             int lane) {
+  const int cur = gp_forward_one(obs, nullptr, params, P, GP_ACT_RELU, act, lane);
   int best = 0;
-  if (lane == 0) best = gp_choose(act + cur * W, P.width[P.n_layers], eps, seed, decision, gid, nullptr);
+  if (lane == 0) best = gp_choose(act + cur * GP_ROW, P.width[P.n_layers], eps, seed, decision, gid, nullptr);
   return __builtin_amdgcn_readfirstlane(best);
 }

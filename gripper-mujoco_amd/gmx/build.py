@@ -22,7 +22,10 @@ def build(verbose: bool = False, force: bool = False, out: str | None = None, ex
     builds, with `extra_flags` added to every compile)."""
     lib_path = out or LIB_PATH
     srcs = [os.path.join(PKG_DIR, s) for s in SOURCES]
-    deps = srcs + [os.path.join(PKG_DIR, "csrc", f) for f in ("gm_kernels.hip", "gm_newton.hip", "gm_math.h", "gm_fphelpers.inc", "gm_policy.hip", "gm_policy_net.h", "gm_ac.hip", "gm_ac_net.h", "gm_state.h")] + \
+    # the device translation units include each other's kernels and headers: every one of
+    # them is a dependency, so code moved between files cannot leave a stale object
+    csrc = os.path.join(PKG_DIR, "csrc")
+    deps = sorted(set(srcs + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".inc"))])) + \
         [os.path.join(REPO_DIR, "include", f) for f in ("gripper_mi355x.h", "gm_settings.def")]
     if not force and out is None and os.path.exists(LIB_PATH):
         t = os.path.getmtime(LIB_PATH)
@@ -32,7 +35,7 @@ def build(verbose: bool = False, force: bool = False, out: str | None = None, ex
     os.makedirs(objdir, exist_ok=True)
     inc = ["-I" + os.path.join(REPO_DIR, "include"), "-I" + os.path.join(PKG_DIR, "csrc")]
     procs, objs = [], []
-    headers = [os.path.join(PKG_DIR, "csrc", "gm_state.h")] + \
+    headers = [os.path.join(csrc, "gm_state.h")] + \
         [os.path.join(REPO_DIR, "include", f) for f in ("gripper_mi355x.h", "gm_settings.def")]
     for src in srcs:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")

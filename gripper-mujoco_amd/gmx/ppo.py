@@ -14,11 +14,11 @@ TrajectoryBuffer.get() and hands new weights back with DeviceActorCritic.set_par
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import numpy as np
 
 from ._lib import load_library
+from .policy import as_f32, linear_init, state_dict_net
 
 DEFAULT_HIDDEN = (64, 64)          # MLPActorCriticPG's default hidden_sizes
 LOG_STD_INIT = -0.5                # MLPGaussianActor
@@ -59,27 +59,13 @@ def noise_draws(seed, gids, decision, n_actions, noise: float) -> np.ndarray:
     return float(noise) * (2.0 * u3 - 1.0)
 
 
-def _linear_init(rng, sizes):
-    parts = []
-    for i in range(len(sizes) - 1):
-        fan_in, fan_out = sizes[i], sizes[i + 1]
-        bound = 1.0 / math.sqrt(fan_in)
-        parts.append(rng.uniform(-bound, bound, size=(fan_out, fan_in)).astype(np.float32).ravel())
-        parts.append(rng.uniform(-bound, bound, size=fan_out).astype(np.float32))
-    return parts
-
-
 def init_params(actor_sizes, critic_sizes, seed: int = 0) -> np.ndarray:
     """nn.Linear's default init for both nets and log_std = -0.5, flattened: the actor's W0
     [out x in], b0, W1, b1, ..., the critic's likewise, then log_std."""
     rng = np.random.default_rng(seed)
-    parts = _linear_init(rng, actor_sizes) + _linear_init(rng, critic_sizes)
+    parts = linear_init(rng, actor_sizes) + linear_init(rng, critic_sizes)
     parts.append(np.full(actor_sizes[-1], LOG_STD_INIT, dtype=np.float32))
     return np.concatenate(parts).astype(np.float32)
-
-
-def _np(t):
-    return np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32)
 
 
 def params_from_state_dict(state_dict):
@@ -90,16 +76,10 @@ def params_from_state_dict(state_dict):
                     key=lambda k: int(k[len(prefix):].split(".")[0]))
         if not ws:
             raise KeyError(f"no {prefix}*.weight in the state dict")
-        sizes = [int(state_dict[ws[0]].shape[1])]
-        parts = []
-        for k in ws:
-            w = _np(state_dict[k])
-            sizes.append(int(w.shape[0]))
-            parts += [w.ravel(), _np(state_dict[k[:-len("weight")] + "bias"]).ravel()]
-        return sizes, parts
+        return state_dict_net(state_dict, ws)
     asz, ap = net("pi.mu_net.")
     csz, cp = net("vf.v_net.")
-    log_std = _np(state_dict["pi.log_std"]).ravel()
+    log_std = as_f32(state_dict["pi.log_std"]).ravel()
     return asz, csz, np.concatenate(ap + cp + [log_std]).astype(np.float32)
 
 

@@ -140,6 +140,39 @@ def test_ac_rollout_equals_per_step(gm, dispatch):
         b.close()
 
 
+def test_ac_rollout_equals_per_step_widest_and_narrowest_layers(gm):
+    """The same identity where the shared forward's indexing is at its limits: actor hidden
+    (256, 3) and critic hidden (3, 256) put width 256 (GP_MAX_WIDTH: 16 output tiles, then 64
+    k-steps up to the row stride) and width 3 (one partial tile, then k padded to 4) in both
+    positions.  33 envs: two full 16-env tiles and a one-env tail in the batched kernel;
+    2-step episodes, so truncation, the bootstrap value and the in-launch reset occur."""
+    if not gpu_available():
+        pytest.skip("no GPU")
+    import torch
+    from gmx.ppo import DeviceActorCritic, TrajectoryBuffer
+    n, k, mx = 33, 3, 2
+    ra = torch.zeros((k, n, 3), dtype=torch.int32, device="cuda")
+    rb = torch.zeros((k, n, 3), dtype=torch.int32, device="cuda")
+    a, b = make_env(gm, n=n), make_env(gm, n=n)
+    pa, pb = (DeviceActorCritic(e, hidden=(256, 3), hidden_v=(3, 256), seed=3) for e in (a, b))
+    ta, tb = TrajectoryBuffer(a, k), TrajectoryBuffer(b, k)
+    try:
+        per_step(a, pa, ta, ra, 0, k, max_ep=mx)
+        pa.finish(ta)
+        pb.rollout(tb, sample=True, noise=NOISE, seed=PSEED, decision0=DEC0, max_episode_steps=mx,
+                   records_dev_ptr=rb.data_ptr())
+        sa, sb = snapshot(a, ta, ra), snapshot(b, tb, rb)
+        assert_same(gm, sa, sb)
+        assert b.dispatch_info()["chunk"] > 0                                   # the fused launch, not its fallback
+        assert (sa["end"] == 2).any() and ((sa["boot"] != 0) == (sa["end"] == 2)).all()
+        assert len(np.unique(sa["mu"])) > n and (sa["val"] != 0).all() and (sa["last_val"] != 0).all()
+    finally:
+        pa.close()
+        pb.close()
+        a.close()
+        b.close()
+
+
 def test_ac_rollout_equals_per_step_full_size(gm):
     """The same identity at the headline batch (4096 envs, every XCD's queue busy), with
     3-step episodes so every env is truncated and reset inside the launch."""

@@ -112,6 +112,43 @@ def test_policy_rollout_equals_per_step(gm, dispatch):
         b.close()
 
 
+def test_policy_rollout_equals_per_step_widest_and_narrowest_layers(gm):
+    """The same identity where the shared forward's indexing is at its limits: layers
+    [63, 256, 3, 8] put width 256 (GP_MAX_WIDTH: 16 output tiles, then 64 k-steps up to the row
+    stride) and width 3 (one partial tile, then k padded to 4) behind each other.  33 envs: two
+    full 16-env tiles and a one-env tail in the batched kernel; 2-step episodes, so envs are
+    truncated and reset inside the launch."""
+    if not gpu_available():
+        pytest.skip("no GPU")
+    import torch
+    from gmx.policy import DevicePolicy
+    n, k, mx = 33, 3, 2
+    ra = torch.zeros((k, n, 3), dtype=torch.int32, device="cuda")
+    rb = torch.zeros((k, n, 3), dtype=torch.int32, device="cuda")
+    a, b = make_env(gm, n=n), make_env(gm, n=n)
+    sizes = [a.n_obs, 256, 3, a.n_actions]
+    assert sizes == [63, 256, 3, 8]
+    pa, pb = DevicePolicy(a, sizes=sizes, seed=3), DevicePolicy(b, sizes=sizes, seed=3)
+    try:
+        acts = per_step(a, pa, ra, 0, k, max_ep=mx)
+        pb.rollout(eps_schedule(0, k), seed=PSEED, decision0=DEC0, max_episode_steps=mx, records_dev_ptr=rb.data_ptr())
+        sa, sb = snapshot(a, ra), snapshot(b, rb)
+        va, vb = gm.env_state_view(sa[1]), gm.env_state_view(sb[1])
+        for f in va.dtype.names:
+            np.testing.assert_array_equal(va[f], vb[f], err_msg=f)
+        assert sa[0] == sb[0]
+        for i in range(2, 6):
+            np.testing.assert_array_equal(sa[i], sb[i])
+        assert b.dispatch_info()["chunk"] > 0                   # the fused launch, not its fallback
+        assert len(np.unique(np.concatenate(acts))) >= 2
+        assert int((sa[5][..., 1] > 0).sum()) >= n              # every env's episode ended inside
+    finally:
+        pa.close()
+        pb.close()
+        a.close()
+        b.close()
+
+
 def test_policy_rollout_greedy_differs_from_random(gm):
     """eps = 0 (greedy) and eps = 1 (uniform) fused rollouts take different actions."""
     if not gpu_available():

@@ -18,7 +18,7 @@ import tempfile
 
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-FUNCS = ("ac_rollout_driver", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel")
+FUNCS = ("ac_rollout_driver", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel", "gm_policy_kernel")
 
 
 def tool(name, *args):
