@@ -691,11 +691,11 @@ __device__ void newton_point(SharedT<CL>& S, const gm_model* __restrict__ m, con
   unsigned long long t0 = prof ? clock64() : 0;
   const int ncon = S.ncon, nl = S.nl;
   // ---- contact lanes: Q = sum_e D u u^T and F = sum_e D aref u over the active edges
+  real Q[6] = {0, 0, 0, 0, 0, 0}, F[3] = {0, 0, 0};
   if (lane < ncon) {
     const real* C = S.con[lane];
     real t2[3];
     cross3(t2, C + 4, C + 7);
-    real Q[6] = {0, 0, 0, 0, 0, 0}, F[3] = {0, 0, 0};
 #pragma unroll
     for (int ed = 0; ed < 4; ed++) {
       real u[3];
@@ -713,6 +713,53 @@ __device__ void newton_point(SharedT<CL>& S, const gm_model* __restrict__ m, con
     qf[6] = F[0]; qf[7] = F[1]; qf[8] = F[2];
   }
   GM_WAVE_SYNC();
+  // ---- the object's ground contacts (its other contacts reach it through the base
+  // composite).  Each contact lane of the object-ground pair forms its own K and F from the
+  // Q / F it still holds and hands the 27 values over in the chain-root stage (dead until
+  // the roots are written below; QF stays as it is for the ground pass); lane k < 27 then
+  // sums entry k over the pair's slots in order, starting from 0: the serial loop's
+  // additions, operand for operand (sg = +-1 makes sg * Fs exact, fused or not).  Eight
+  // contacts fill the stage, so a longer pair takes further rounds (a plane pair makes at
+  // most four: one round).
+  {
+    static_assert(sizeof(S.st.root) >= sizeof(real) * 8 * 27, "ground composites: eight contacts per round in the chain-root stage");
+    real (*gs)[27] = reinterpret_cast<real (*)[27]>(&S.st.root[0][0]);
+    const int pr = T->pair_gobj;
+    int c0 = 0, c1 = 0;
+    if (pr >= 0) {
+      c0 = __builtin_amdgcn_readfirstlane((int)S.pair_off[pr]);
+      c1 = c0 + __builtin_amdgcn_readfirstlane((int)S.pair_cnt[pr]);
+      if (c1 > ncon) c1 = ncon;
+    }
+    real gacc = 0;
+    for (int r0 = c0; r0 < c1; r0 += 8) {
+      if (r0 > c0) GM_WAVE_SYNC();   // (the round before is summed)
+      if (lane >= r0 && lane < r0 + 8 && lane < c1) {
+        const real qf[9] = {Q[0], Q[1], Q[2], Q[3], Q[4], Q[5], F[0], F[1], F[2]};
+        const real pos[3] = {S.con[lane][1], S.con[lane][2], S.con[lane][3]};
+        const real sg = (S.cbody[lane][1] == T->body_obj) ? 1.0 : -1.0;
+        real Kc[21], Fs[6];
+        spatial_K(qf, pos, Kc);
+        cross3(Fs, pos, qf + 6);
+        Fs[3] = qf[6]; Fs[4] = qf[7]; Fs[5] = qf[8];
+        real* g = gs[lane - r0];
+#pragma unroll
+        for (int k = 0; k < 21; k++) g[k] = Kc[k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) g[21 + k] = sg * Fs[k];
+      }
+      GM_WAVE_SYNC();
+      if (lane < 27) {
+        real v[8];   // (all eight slots read in one batch; those past the pair are selected away)
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = gs[j][lane];
+        keep_n<8>(v);
+#pragma unroll
+        for (int j = 0; j < 8; j++) gacc = (r0 + j < c1) ? gacc + v[j] : gacc;
+      }
+    }
+    if (lane < 27) S.go[lane] = gacc;
+  }
   // ---- scan lanes: the body's contacts with the object.  Contacts of gripper bodies with
   // the ground (rare) are added in a second pass below, so the common path keeps one
   // 27-value composite per lane in registers instead of two.
@@ -761,37 +808,6 @@ __device__ void newton_point(SharedT<CL>& S, const gm_model* __restrict__ m, con
   // zero and their Hessian entries are H~'s own
   const bool any_o = __ballot(have_o) != 0ull;
   PH(3);
-  // the object's ground contacts (its other contacts reach it through the base composite)
-  if (lane == T->lane_obj) {
-    real Kgo[21], Fgo[6];
-#pragma unroll
-    for (int k = 0; k < 21; k++) Kgo[k] = 0;
-#pragma unroll
-    for (int k = 0; k < 6; k++) Fgo[k] = 0;
-    const int pr = T->pair_gobj;
-    if (pr >= 0) {
-      const int c0 = S.pair_off[pr];
-      int c1 = c0 + S.pair_cnt[pr];
-      if (c1 > ncon) c1 = ncon;
-      for (int c = c0; c < c1; c++) {
-        const real* qf = S.nw.QF[c];
-        const real pos[3] = {S.con[c][1], S.con[c][2], S.con[c][3]};
-        const real sg = (S.cbody[c][1] == T->body_obj) ? 1.0 : -1.0;
-        real Kc[21], Fs[6];
-        spatial_K(qf, pos, Kc);
-        cross3(Fs, pos, qf + 6);
-        Fs[3] = qf[6]; Fs[4] = qf[7]; Fs[5] = qf[8];
-#pragma unroll
-        for (int k = 0; k < 21; k++) Kgo[k] += Kc[k];
-#pragma unroll
-        for (int k = 0; k < 6; k++) Fgo[k] += sg * Fs[k];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 21; k++) S.go[k] = Kgo[k];
-#pragma unroll
-    for (int k = 0; k < 6; k++) S.go[21 + k] = Fgo[k];
-  }
   // ---- suffix sums along the chains (composite, like Ic)
   if (any_o) {
 #pragma unroll
