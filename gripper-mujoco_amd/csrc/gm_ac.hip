@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64) void gm_ac_kernel(int what, const float* __rest
   }
   if (what == 1) {
     int end = 0;
-    if (mine) end = done[env] ? 1 : (max_ep > 0 && states[env].num_action_steps >= max_ep) ? 2 : 0;
+    if (mine) end = gm_episode_end_code(done[env], states[env].num_action_steps, max_ep);
     float b = 0.0f;
     if (__ballot(end == 2) != 0ull) {   // (wave-uniform) some env of the tile was truncated
       const int cur = gp_forward_tile(obs, nullptr, e0, n_envs, cparams, A.net.critic, A.net.act_critic, act, lane);

@@ -127,54 +127,19 @@ bool nseg_supported(int n) {
     default: return false;
   }
 }
-struct RolloutArgs {
-  int steps, act_mode;
-  uint64_t act_seed;
-  float jitter;
-  int max_ep;
-  gm_episode_end* rec;
-  // act_mode 2 (gm_policy_rollout): the packed network, its layout, eps per env-step
-  const float* pparams = nullptr;
-  GpNet pnet{};
-  const float* peps = nullptr;
-  uint64_t pdecision = 0;
-  // act_mode 5 (gm_ac_rollout): the device copy of the launch's actor-critic arguments
-  const GaArgs* ac = nullptr;
-};
-hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, const RolloutArgs* roll = nullptr) {
+// job: a rollout's (rollout_job; it needs the chunked queue), NULL: one plain env-step per env
+hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, const GmRolloutJob* job = nullptr) {
   // the full env-step (mode 0) runs in cost-sorted order and records each env's cost
   const int32_t* order = (mode == 0 && grid == c->n_envs) ? c->d_order : nullptr;
   uint32_t* cost = (mode == 0 && grid == c->n_envs) ? c->d_cost : nullptr;
-  // the chunked work queue (gm_kernels.hip chunked_env_steps): one workgroup per resident
-  // wave slot, each pulling env chunks until every env has finished
+  // the chunked work queue (gm_chunkq.h, gm_kernels.hip chunked_env_steps): one workgroup per
+  // resident wave slot, each pulling env chunks until every env has finished
   const bool chunked = order && c->chunk > 0 && c->chunk_grid > 0 && dbg.phase == nullptr;
   GmChunkQ q{c->d_chunk_ctr, c->d_chunk_ring, c->d_chunk_carry, c->chunk_cap, chunked ? c->chunk : 0,
-             c->chunk_margin, c->chunk_yields, c->chunk_cmargin, c->d_chunk_st};
-  q.steal = c->chunk_steal;
-  q.prio = c->chunk_prio;
-  q.steps = 1;
-  q.act_mode = -1;   // gm_step: one plain env-step per env (gm_rollout sets the rollout fields)
-  if (roll && chunked) {
-    q.steps = roll->steps;
-    q.act_mode = roll->act_mode;
-    q.act_seed = roll->act_seed;
-    q.jitter = roll->jitter;
-    q.max_ep = roll->max_ep;
-    q.rec = roll->rec;
-    q.eq = c->d_eq;
-    q.objs = c->d_objs;
-    q.n_objects = c->n_objects;
-    q.scene = c->d_scene;
-    q.scene_tries = c->scene_tries;
-    q.sr = c->spawn_rand;
-    q.sr.env_offset = c->env_offset;   // (the driver's global env ids even without random spawns)
-    q.pparams = roll->pparams;
-    q.pnet = roll->pnet;
-    q.peps = roll->peps;
-    q.pseed = roll->act_seed;
-    q.pdecision = roll->pdecision;
-    q.ac = roll->ac;
-  }
+             c->chunk_margin, c->chunk_yields, c->chunk_cmargin, c->d_chunk_st, c->chunk_steal, c->chunk_prio};
+  q.job.steps = 1;
+  q.job.driver = GM_DRV_NONE;
+  if (job && chunked) q.job = *job;
   if (chunked) grid = c->chunk_grid;
   // the env-step proper (not the settle, a diagnostic substep or a profiled step) on DUO
   // workgroups when the context chose them; the chunked grid was sized for that kernel
@@ -196,7 +161,43 @@ hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, 
     default: return hipErrorInvalidValue;
   }
 }
-
+// The timed env-step launch (gm_step, and the rollouts' one persistent launch of job->steps
+// env-steps per env) and the next launch's dispatch order
+int timed_launch(gm_ctx* c, const GmRolloutJob* job) {
+  DebugOut dbg{nullptr, nullptr, nullptr, nullptr, nullptr};
+  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+  HIPCHK(c, launch_step(c, c->n_envs, c->n_envs, 0, dbg, job));
+  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+  hipLaunchKernelGGL(gm_dispatch_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_cost, c->d_order, c->n_envs,
+                     c->d_chunk_ctr, c->d_chunk_st);
+  HIPCHK(c, hipGetLastError());
+  c->timed = true;
+  c->last_launch_steps = job ? job->steps : 1;
+  return GM_OK;
+}
+// A rollout entry point runs as one persistent launch of a rollout_job when the queue is on ...
+bool chunk_queue_on(const gm_ctx* c) { return c->chunk > 0 && c->chunk_grid > 0; }
+GmRolloutJob rollout_job(const gm_ctx* c, int steps, GmDriver driver, uint64_t seed, float jitter, int max_ep,
+                         gm_episode_end* rec) {
+  GmRolloutJob j{steps, driver, seed, jitter, max_ep, rec, c->d_eq, c->d_objs, c->n_objects, c->scene_tries,
+                 c->d_scene, c->spawn_rand};
+  j.sr.env_offset = c->env_offset;   // (the driver's global env ids even without random spawns)
+  return j;
+}
+// ... and with the one-shot kernel (GM_CHUNK_SUBSTEPS=0) as the per-step sequence the launch
+// fuses: the driver's before(k) -> gm_step -> its after(k) -> gm_autoreset_episodes
+template <class Before, class After>
+int per_step_rollout(gm_ctx* c, int n_steps, int max_ep, gm_episode_end* records, Before before, After after) {
+  for (int k = 0; k < n_steps; k++) {
+    int rc = before(k);
+    if (rc == GM_OK) rc = gm_step(c);
+    if (rc == GM_OK) rc = after(k);
+    if (rc == GM_OK) rc = gm_autoreset_episodes(c, max_ep, nullptr, 1, nullptr,
+                                                records ? records + (size_t)k * c->n_envs : nullptr);
+    if (rc != GM_OK) return rc;
+  }
+  return GM_OK;
+}
 
 int build_topo(const gm_model& m, GmTopo& T, std::string& err) {
   std::memset(&T, 0, sizeof(T));
@@ -762,42 +763,26 @@ int gm_random_actions(gm_ctx* c, uint64_t seed, float* out, int on_device) {
   return GM_OK;
 }
 
-// the persistent rollout launch (gm_rollout, gm_policy_rollout) and the next launch's order
-static int rollout_launch(gm_ctx* c, const RolloutArgs& ra) {
-  DebugOut dbg{nullptr, nullptr, nullptr, nullptr, nullptr};
-  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  HIPCHK(c, launch_step(c, c->n_envs, c->n_envs, 0, dbg, &ra));
-  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-  hipLaunchKernelGGL(gm_dispatch_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_cost, c->d_order, c->n_envs,
-                     c->d_chunk_ctr, c->d_chunk_st);
-  HIPCHK(c, hipGetLastError());
-  c->timed = true;
-  c->last_launch_steps = ra.steps;
-  return GM_OK;
-}
-
 int gm_rollout(gm_ctx* c, int n_steps, const gm_rollout_params* p, gm_episode_end* records) {
   if (!c || !p || n_steps < 1 ||
-      (p->action_mode != 0 && p->action_mode != 1 && p->action_mode != 3 && p->action_mode != 4))
+      (p->action_mode != GM_DRV_SCRIPT && p->action_mode != GM_DRV_RANDOM && p->action_mode != GM_DRV_PROGRAM &&
+       p->action_mode != GM_DRV_MIX))
     return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->chunk > 0 && c->chunk_grid > 0) {
-    // one persistent launch: every env runs its n_steps env-steps back to back
-    const RolloutArgs ra{n_steps, p->action_mode, p->seed, p->jitter, p->max_episode_steps, records};
-    return rollout_launch(c, ra);
+  if (chunk_queue_on(c)) {
+    const GmRolloutJob job = rollout_job(c, n_steps, (GmDriver)p->action_mode, p->seed, p->jitter,
+                                         p->max_episode_steps, records);
+    return timed_launch(c, &job);
   }
-  // the one-shot kernel (GM_CHUNK_SUBSTEPS=0): the same sequence as per-step launches
-  for (int k = 0; k < n_steps; k++) {
-    int rc = p->action_mode == 0 ? gm_scripted_actions(c, p->seed, p->jitter, c->d_act, 1)
-             : p->action_mode == 1 ? gm_random_actions(c, p->seed, c->d_act, 1)
-                                   : gm_program_actions(c, p->seed, p->jitter, p->action_mode, c->d_act, 1);
-    if (rc == GM_OK) rc = gm_set_action(c, c->d_act, 1);
-    if (rc == GM_OK) rc = gm_step(c);
-    if (rc == GM_OK) rc = gm_autoreset_episodes(c, p->max_episode_steps, nullptr, 1, nullptr,
-                                                records ? records + (size_t)k * c->n_envs : nullptr);
-    if (rc != GM_OK) return rc;
-  }
-  return GM_OK;
+  return per_step_rollout(
+      c, n_steps, p->max_episode_steps, records,
+      [&](int) {
+        const int rc = p->action_mode == GM_DRV_SCRIPT   ? gm_scripted_actions(c, p->seed, p->jitter, c->d_act, 1)
+                       : p->action_mode == GM_DRV_RANDOM ? gm_random_actions(c, p->seed, c->d_act, 1)
+                                                         : gm_program_actions(c, p->seed, p->jitter, p->action_mode, c->d_act, 1);
+        return rc == GM_OK ? gm_set_action(c, c->d_act, 1) : rc;
+      },
+      [](int) { return (int)GM_OK; });
 }
 
 int gm_set_random_spawn(gm_ctx* c, int enable, uint64_t seed, int position_noise_mm, int rotation_noise_deg) {
@@ -1014,25 +999,16 @@ int gm_calibrate(const gm_model* model, const gm_config* cfg, const gm_object* o
 int gm_step(gm_ctx* c) {
   if (!c) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  DebugOut dbg{nullptr, nullptr, nullptr, nullptr, nullptr};
-  HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  HIPCHK(c, launch_step(c, c->n_envs, c->n_envs, 0, dbg));
-  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-  hipLaunchKernelGGL(gm_dispatch_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_cost, c->d_order, c->n_envs,
-                     c->d_chunk_ctr, c->d_chunk_st);
-  HIPCHK(c, hipGetLastError());
-  c->timed = true;
-  c->last_launch_steps = 1;
-  return GM_OK;
+  return timed_launch(c, nullptr);
 }
 
 int gm_chunk_claim_waits(gm_ctx* c, uint32_t* out2) {
   if (!c || !out2) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  uint32_t w[2];
-  HIPCHK(c, hipMemcpyAsync(w, c->d_chunk_ctr + GM_CQ_LAST + 37, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  uint32_t w[GM_CQC_N];   // the last launch's counters (gm_chunkq.h GmCqCounter)
+  HIPCHK(c, hipMemcpyAsync(w, c->d_chunk_ctr + GM_CQ_LAST, sizeof(w), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  out2[0] = w[0]; out2[1] = w[1];
+  out2[0] = w[GM_CQC_CLAIM_WAITS]; out2[1] = w[GM_CQC_CLAIM_POLLS];
   return GM_OK;
 }
 
@@ -1053,14 +1029,16 @@ int gm_chunk_job_stats(gm_ctx* c, uint32_t* clk, int32_t* yields) {
 int gm_chunk_stats(gm_ctx* c, uint32_t* out, uint64_t* times) {
   if (!c || !out) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  uint32_t w[37];
+  uint32_t w[GM_CQC_N];
   HIPCHK(c, hipMemcpyAsync(w, c->d_chunk_ctr + GM_CQ_LAST, sizeof(w), hipMemcpyDeviceToHost, c->stream));
-  if (times) HIPCHK(c, hipMemcpyAsync(times, c->d_chunk_st + 8, sizeof(uint64_t) * 5, hipMemcpyDeviceToHost, c->stream));
+  if (times)
+    HIPCHK(c, hipMemcpyAsync(times, c->d_chunk_st + GM_CQT_LAST, sizeof(uint64_t) * GM_CQT_N, hipMemcpyDeviceToHost,
+                             c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  out[0] = std::min<uint32_t>(w[0], (uint32_t)c->n_envs);
-  out[1] = w[32]; out[2] = w[33]; out[3] = w[34];
+  out[0] = std::min<uint32_t>(w[GM_CQC_FRESH], (uint32_t)c->n_envs);
+  out[1] = w[GM_CQC_DONE]; out[2] = w[GM_CQC_YIELDS]; out[3] = w[GM_CQC_RESUMES];
   out[4] = (uint32_t)c->chunk; out[5] = (uint32_t)c->chunk_grid;
-  out[6] = w[36];
+  out[6] = w[GM_CQC_STEALS];
   return GM_OK;
 }
 
@@ -1068,7 +1046,8 @@ int gm_chunk_timeline(gm_ctx* c, uint64_t* out, int max_out) {
   if (!c || !out || max_out < 0) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   const int n = std::min(max_out, c->chunk_grid + 2 * c->n_envs);
-  HIPCHK(c, hipMemcpyAsync(out, c->d_chunk_st + 16, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->d_chunk_st + GM_CQT_TIMELINE, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost,
+                           c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return n;
 }
@@ -1434,7 +1413,7 @@ int gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed
   if (!p || !p->ctx || !eps || n_steps < 1) return GM_E_ARG;
   gm_ctx* c = p->ctx;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->chunk > 0 && c->chunk_grid > 0) {
+  if (chunk_queue_on(c)) {
     if (n_steps > p->eps_cap) {
       // (the stream may still read the old buffer: wait before freeing it)
       HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1447,22 +1426,16 @@ int gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed
     // eps is the caller's (pageable) array: the copy owns its bytes before the call returns
     const int rc = stage_upload(c, p->d_eps, eps, sizeof(float) * (size_t)n_steps);
     if (rc != GM_OK) return rc;
-    RolloutArgs ra{n_steps, 2, seed, 0.0f, max_episode_steps, records};
-    ra.pparams = p->d_params;
-    ra.pnet = p->net;
-    ra.peps = p->d_eps;
-    ra.pdecision = decision0;
-    return rollout_launch(c, ra);
+    GmRolloutJob job = rollout_job(c, n_steps, GM_DRV_DQN, seed, 0.0f, max_episode_steps, records);
+    job.pparams = p->d_params;
+    job.pnet = p->net;
+    job.peps = p->d_eps;
+    job.pdecision = decision0;
+    return timed_launch(c, &job);
   }
-  // the one-shot kernel (GM_CHUNK_SUBSTEPS=0): the per-step sequence it fuses
-  for (int k = 0; k < n_steps; k++) {
-    int rc = gm_policy_act(p, eps[k], seed, decision0 + (uint64_t)k);
-    if (rc == GM_OK) rc = gm_step(c);
-    if (rc == GM_OK) rc = gm_autoreset_episodes(c, max_episode_steps, nullptr, 1, nullptr,
-                                                records ? records + (size_t)k * c->n_envs : nullptr);
-    if (rc != GM_OK) return rc;
-  }
-  return GM_OK;
+  return per_step_rollout(
+      c, n_steps, max_episode_steps, records,
+      [&](int k) { return gm_policy_act(p, eps[k], seed, decision0 + (uint64_t)k); }, [](int) { return (int)GM_OK; });
 }
 
 int gm_policy_read(gm_policy* p, int32_t* actions, float* q) {
@@ -1653,25 +1626,20 @@ int gm_ac_rollout(gm_ac* p, const gm_ac_traj* traj, int n_steps, int sample, flo
   if (!ac_traj_ok(traj) || n_steps < 1 || n_steps > traj->capacity || !(noise >= 0.0f))
     return fail(c, GM_E_ARG, "gm_ac_rollout: incomplete trajectory buffer, n_steps outside its capacity or negative noise");
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->chunk > 0 && c->chunk_grid > 0) {
+  if (chunk_queue_on(c)) {
     GaArgs A{};
     ac_fill(A, p, traj, sample, noise, seed, decision0);
     const int rc = stage_upload(c, p->d_args, &A, sizeof(GaArgs));
     if (rc != GM_OK) return rc;
-    RolloutArgs ra{n_steps, 5, seed, 0.0f, max_episode_steps, records};
-    ra.ac = p->d_args;
-    return rollout_launch(c, ra);
+    GmRolloutJob job = rollout_job(c, n_steps, GM_DRV_AC, seed, 0.0f, max_episode_steps, records);
+    job.ac = p->d_args;
+    return timed_launch(c, &job);
   }
-  // the one-shot kernel (GM_CHUNK_SUBSTEPS=0): the per-step sequence it fuses
-  for (int k = 0; k < n_steps; k++) {
-    int rc = gm_ac_act(p, traj, k, sample, noise, seed, decision0 + (uint64_t)k);
-    if (rc == GM_OK) rc = gm_step(c);
-    if (rc == GM_OK) rc = gm_ac_record(p, traj, k, max_episode_steps);
-    if (rc == GM_OK) rc = gm_autoreset_episodes(c, max_episode_steps, nullptr, 1, nullptr,
-                                                records ? records + (size_t)k * c->n_envs : nullptr);
-    if (rc != GM_OK) return rc;
-  }
-  return gm_ac_finish(p, traj, n_steps - 1);
+  const int rc = per_step_rollout(
+      c, n_steps, max_episode_steps, records,
+      [&](int k) { return gm_ac_act(p, traj, k, sample, noise, seed, decision0 + (uint64_t)k); },
+      [&](int k) { return gm_ac_record(p, traj, k, max_episode_steps); });
+  return rc == GM_OK ? gm_ac_finish(p, traj, n_steps - 1) : rc;
 }
 
 int gm_ac_gae(gm_ctx* c, const gm_ac_traj* traj, int n_steps, float gamma, float lam, float* adv, float* ret) {

@@ -72,7 +72,6 @@ __device__ __forceinline__ void keep_n(const double* a) {
   }
 #undef GM_K
 }
-#define GM_CQ_NB 16      // priority buckets per XCD of the chunked env-step (gm_step_kernel)
 #define GM_BB_SLOTS 18   // box-box hit slots in the LDS union (18 x 256 B; SharedT asserts it fits
                          // inside the union's CL-independent chain-root stage, so it never grows LDS)
 // gm_step_kernel is instantiated per finger chain length (CL = n_seg + 2) so every chain
@@ -2029,53 +2028,8 @@ __device__ __noinline__ void monitor_call(GM_AS_LDS SharedT<CL>* S_, const GM_AS
   monitor_sensors<CL>(*(SharedT<CL>*)S_, (const gm_model*)uniform_const_ptr(m_), (const gm_config*)uniform_const_ptr(C_),
                       (const GmTopo*)uniform_const_ptr(T_), lane);
 }
-// Preemption test of the chunked env-step (chunked_env_steps): every `every` substeps the
-// loop yields when the predicted work left in this env, own * left / total (the env's last
-// dispatch cost, shader clocks / 64, spread evenly over its substeps), has dropped below the
-// next unstarted env's cost -- longest-remaining-work-first at substep granularity.
-struct GmPreempt {
-  const uint32_t* fresh_head;   // the queue's next-unstarted index (agent-scope loads)
-  const int32_t* order;
-  const uint32_t* cost;
-  uint32_t n, own;
-  int left, total, every;       // every = 0: never yield
-  int margin;                   // percent
-  // the XCD's yielded envs: a running env also yields to the best bucket when that bucket's
-  // lower edge (cmax * b / GM_CQ_NB) exceeds its own work left by cmargin percent (< 0: off)
-  const uint32_t* bq;
-  uint32_t cmax;
-  int cmargin;
-  int prio;                     // > 0: the wave's issue priority follows the work left (job_prio)
-  int steps;                    // env-steps per job: the cost array holds per-env-step costs
-};
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// The wave's VALU issue priority from its job's predicted work left (rem, in the cost array's
-// units) against the launch's heaviest job (cmax): 0..3 in quarters.  Two waves share a SIMD's
-// issue and it goes by priority, then age (MI355X_MICROARCH.md, two waves per SIMD) -- the
-// persistent grid's waves never change age, so without this the job with the most work left
-// runs at the younger wave's pace on half the SIMDs.  Longest-remaining-work-first, at issue.
-__device__ __forceinline__ void job_prio(uint64_t rem, uint32_t cmax, int mode) {
-  if (mode <= 0) return;
-  const uint32_t p = __builtin_amdgcn_readfirstlane((uint32_t)(rem * 4u / (uint64_t)(cmax ? cmax : 1u)));
-  if (p >= 3) __builtin_amdgcn_s_setprio(3);
-  else if (p == 2) __builtin_amdgcn_s_setprio(2);
-  else if (p == 1) __builtin_amdgcn_s_setprio(1);
-  else __builtin_amdgcn_s_setprio(0);
-}
-// Claim the next entry of a yielded-env bucket (head at b[0], tail at b[1]; lane 0): the head
-// advances only while it is below the tail, so every claimed slot was reserved by a producer
-// that is about to store it -- two waves that saw the same last entry cannot both claim, and
-// the loser parks on no slot that a future yield would have to fill.  Returns the slot or -1.
-__device__ __forceinline__ int64_t claim_bucket(uint32_t* b) {
-  uint32_t h = ld_agent(b);
-  for (;;) {
-    if (h >= ld_agent(b + 1)) return -1;
-    if (__hip_atomic_compare_exchange_strong(b, &h, h + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      return (int64_t)h;
-  }
-}
+// the chunked work queue: GmRolloutJob, GmChunkQ, GmPreempt and the scheduler's pieces
+#include "gm_chunkq.h"
 // returns the substeps run (nsub unless the preemption test yielded).  PROF = false
 // compiles the per-phase clock reads (PH) out: no uniform branch at every phase boundary,
 // so the scheduler's regions span them (the env-step kernel's chunked path runs this one)
@@ -2539,100 +2493,8 @@ __device__ __forceinline__ void store_state(const SharedT<CL>& S, GmEnvState* __
   for (int i = lane; i < GM_HOT_WORDS; i += NT) dst[i] = src[i];
 }
 
-// ---------------------------------------------------------------- chunked env-step
-// gm_step as a persistent work queue over env CHUNKS of a few substeps (DESIGN.md §5,
-// "Chunked dispatch").  One env-step is ~2.9 ms on a wave; with 4096 envs on 2048 resident
-// waves, whole env-steps leave the chip partly idle for the last third of the launch (the
-// last env starts ~5 ms in).  Here a wave runs one chunk of an env, stores the env's hot
-// state and hands the env on; any wave of the same XCD continues it.  Results are
-// bit-identical to the one-shot kernel: the substeps, their order and the epilogue are the
-// same code on the same state.
-//
-// Scheduling: envs start in descending predicted cost (the previous env-step's); a running
-// env yields (at most max_yields times per env-step) when an unstarted env has clearly more
-// work than it has left, and yielded envs wait in priority buckets by predicted work left;
-// a free wave takes the larger of the best bucket's head and the next unstarted env --
-// longest-remaining-work-first at substep granularity (tools/sim_dispatch.py).
-//
-// Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility): an env's chunks all run on
-// the XCD that started it (each XCD has its own continuation buckets, a wave serves those
-// of the XCD it runs on, read from HW_REG_XCC_ID), so the L2 is shared between producer and
-// consumer.  Producer: plain stores of the state and carry, s_waitcnt vmcnt(0), then the
-// ring entry by an agent-scope (sc1) store.  Consumer: sc1 poll of the entry, agent-scope
-// acquire (invalidates its CU's L1) and its wait, then plain loads.
-struct GmChunkCarry {        // what a chunk hands the next besides the hot state
-  int32_t sub_done, nsub;
-  int32_t work_nefc, work_mpr, work_newton, stp_fixed;
-  uint32_t clk;              // s_memtime / 64 summed over this env-step's chunks
-  int32_t yielded;           // yields so far this env-step (at most GmChunkQ::max_yields)
-  int32_t steps_left;        // env-steps of this launch's job still to run, the current one included
-  int32_t step_idx;          // index of the current env-step in the launch (rollout records)
-  int32_t job_yields;        // yields over the whole job (gm_chunk_job_stats)
-};
-// counters (zeroed by gm_dispatch_order_kernel before every launch), one 128-B line each:
-// ring r = x * GM_CQ_NB + bucket: [r * 32] its head, [r * 32 + 1] its tail; GM_CQ_FRESH the
-// next unstarted env, GM_CQ_DONE envs finished, + 1 yields, + 2 resumes, + 4 resumes on another
-// XCD, + 5 claims whose ring slot was still empty (the producer between its tail increment and
-// its entry store), + 6 polls those claims made; GM_CQ_LAST the previous launch's
-// [GM_CQ_FRESH ..] (39 words, diagnostics)
-#define GM_CQ_FRESH (8 * GM_CQ_NB * 32)
-#define GM_CQ_DONE (GM_CQ_FRESH + 32)
-#define GM_CQ_CMAX (GM_CQ_DONE + 3)   // this launch's bucket scale (written by the order kernel)
-#define GM_CQ_WORDS (GM_CQ_FRESH + 64)
-#define GM_CQ_LAST GM_CQ_WORDS
-#define GM_CQ_ALLOC (GM_CQ_WORDS + 64)
-struct GmChunkQ {
-  uint32_t* ctr;             // GM_CQ_ALLOC words
-  uint64_t* ring;            // [8 * GM_CQ_NB][cap] (predicted work left << 32) | (env + 1), 0 = empty
-  GmChunkCarry* carry;       // [n_envs]
-  int cap;                   // ring slots per XCD: n_envs + launched waves
-  int chunk;                 // substeps between preemption tests
-  int margin;                // yield when work left * (100 + margin) < next unstarted env's * 100
-  int max_yields;            // per env per env-step
-  int cmargin;               // yield to a yielded env with cmargin percent more work left (< 0: off)
-  unsigned long long* st;    // [0] first pick, [1] first pick that found no unstarted env,
-                             // [2] last env finished (100 MHz clock), [3] wave-busy, [4] wave
-                             // polling (sums, 100 MHz ticks); [8 ..] the previous launch's;
-                             // [16 + w] when workgroup w finished its last piece of work
-  // rollout (gm_rollout; act_mode < 0: one plain env-step per env, gm_step): each env runs
-  // `steps` env-steps in a row, every one of them the per-step API's sequence -- driver actions
-  // (gm_scripted_actions / gm_random_actions) -> set_continous_action -> action_step + obs /
-  // done / reward -> gm_autoreset_episodes' episode-end record and reset
-  int steps;
-  int act_mode;              // -1 none (gm_step); 0 scripted grasp mix, 1 uniform random, 3 grasp program,
-                             // 4 program / scripted mix (gm_rollout); 2 DQN policy (gm_policy_rollout);
-                             // 5 PPO actor-critic (gm_ac_rollout)
-  uint64_t act_seed;
-  float jitter;
-  int max_ep;                // truncation (num_action_steps >= max_ep), <= 0 off
-  gm_episode_end* rec;       // [steps][n_envs] episode-end records (may be NULL)
-  const double* eq;          // the settled equilibrium (calibrate_reset) for the resets
-  const gm_object* objs;
-  int n_objects;
-  int scene_tries;
-  const gm_spawn_params* scene;
-  GmSpawnRand sr;
-  int steal;                 // an idle wave may resume a yielded env of another XCD
-  int prio;                  // > 0: issue priority by predicted work left (job_prio)
-  // act_mode 2: the DQN policy picks each env-step's discrete action on the env's own wave
-  // (gm_policy_rollout; gp_select_one = gm_policy_kernel's select_action for one env)
-  const float* pparams;      // packed network (gm_policy_pack layout)
-  GpNet pnet;
-  const float* peps;         // [steps] exploration threshold per env-step of the launch
-  uint64_t pseed, pdecision; // the policy's seed and the first env-step's decision index
-  // act_mode 5: the PPO actor-critic samples each env-step's continuous action on the env's own
-  // wave and fills the trajectory buffer (gm_ac_rollout; ac_rollout_driver)
-  const GaArgs* ac;          // device copy of the launch's arguments
-};
-__device__ __forceinline__ void st_agent(uint64_t* p, uint64_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t ld_agent64(const uint64_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t add_agent(uint32_t* p, uint32_t v) {
-  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// ------------------------------ chunked env-step: the rollout job (its work queue: gm_chunkq.h)
+
 
 // what survives a reset (see reset_env)
 struct GmResetKeep {
@@ -2665,12 +2527,12 @@ __device__ __forceinline__ gm_program_in program_input(const GmEnvHot& s, RingRe
   in.palm = ring_latest(s, R, ST_SI_PALM);
   return in;
 }
-// the driver's fraction for action i of kind `kind` (modes: 0 scripted grasp mix, 1 uniform
-// random, 3 grasp program, 4 the program in 1 episode of 4 and the scripted mix otherwise)
+// the scripted drivers' fraction for action i of kind `kind` (mode: GM_DRV_SCRIPT, _RANDOM,
+// _PROGRAM or _MIX)
 __device__ __forceinline__ float driver_fraction(const GmEnvHot& s, RingRef R, const gm_model* __restrict__ m,
                                                  const gm_config* __restrict__ C, int mode, uint64_t seed, float jitter,
                                                  int64_t gid, int i, int kind) {
-  if (mode == 3 || (mode == 4 && gm_program_episode(seed, gid, s.episode))) {
+  if (mode == GM_DRV_PROGRAM || (mode == GM_DRV_MIX && gm_program_episode(seed, gid, s.episode))) {
     if (kind < 0) return 0.0f;
     const gm_action* acts[GM_N_ACTION_KINDS] = {
 #define GM_AA(n, u, vv, sg) &C->s.n,
@@ -2679,7 +2541,7 @@ __device__ __forceinline__ float driver_fraction(const GmEnvHot& s, RingRef R, c
     const gm_program_in in = program_input(s, R, m);
     return gm_program_fraction(&in, kind, acts[kind]->value, acts[kind]->sign);
   }
-  if (mode == 0 || mode == 4) return gm_script_fraction(seed, gid, s.episode, s.num_action_steps, i, kind, jitter);
+  if (mode == GM_DRV_SCRIPT || mode == GM_DRV_MIX) return gm_script_fraction(seed, gid, s.episode, s.num_action_steps, i, kind, jitter);
   return gm_random_fraction(seed, gid, s.episode, s.num_action_steps, i);
 }
 // the rollout driver's actions for the env's next env-step (lane 0): the same fractions
@@ -2700,7 +2562,7 @@ __device__ __noinline__ void driver_actions(GmEnvHot& s, RingRef R, const gm_mod
   for (int i = 0; i < na; i++) set_action_one(s, m, C, i, f[i]);
 }
 
-// act_mode 5 (gm_ac_rollout): the actor-critic's part of one env's env-step on the env's own
+// GM_DRV_AC (gm_ac_rollout): the actor-critic's part of one env's env-step on the env's own
 // wave, kept out of the substep loop's instruction stream (called between env-steps only).
 //   phase 0, before the env-step: gm_ac_act on this env alone -- observation, mu, the sampled
 //     action, logp and V(obs) into trajectory row k, then lane 0 applies the clipped actions in
@@ -2743,7 +2605,7 @@ __device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restri
       }
     }
   } else if (phase == 1) {
-    const int end = __builtin_amdgcn_readfirstlane(s.done ? 1 : (max_ep > 0 && s.num_action_steps >= max_ep) ? 2 : 0);
+    const int end = __builtin_amdgcn_readfirstlane(gm_episode_end_code(s.done, s.num_action_steps, max_ep));
     float b = 0.0f;
     if (end == 2) b = ga_value_one(obs, A, scratch, lane);
     if (lane == 0) {
@@ -2757,8 +2619,48 @@ __device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restri
   }
 }
 
+// Where the drivers plug into the queue's env-steps ("The seam between the queue
+// and the drivers"): one env of job J on its wave, its state in the LDS image S, g its HBM record;
+// scratch: the union S.st.  (The begin of an env-step is in chunked_env_steps: a function cost a VGPR.)
+__device__ __forceinline__ int64_t rollout_gid(const GmRolloutJob& J, int env) { return J.sr.env_offset + env; }
+// End env-step k, after the epilogue: gm_autoreset_episodes on this env -- the episode-end
+// record, the actor-critic's trajectory record, then MjEnv.reset and the reset observation
+template <int CL>
+__device__ __forceinline__ void rollout_end_step(SharedT<CL>& S, GmEnvState* g, float* __restrict__ obs, int env,
+                                                 int n_envs, const GmRolloutJob& J, int k, const gm_model* __restrict__ m,
+                                                 const gm_config* __restrict__ C, const GmTopo* __restrict__ T, int lane) {
+  if (J.driver < 0) return;
+  const int end = __builtin_amdgcn_readfirstlane(gm_episode_end_code(S.s.done, S.s.num_action_steps, J.max_ep));
+  if (lane == 0 && J.rec)
+    J.rec[(size_t)k * (uint32_t)n_envs + env] =
+        gm_episode_end_record(end, S.s.cumulative_reward, S.s.num_action_steps, S.s.bev_last[GM_EV_successful_grasp]);
+  if (J.driver == GM_DRV_AC)
+    ac_rollout_driver(1, J.ac, obs + (size_t)env * C->n_obs, env, n_envs, k, J.max_ep, rollout_gid(J, env),
+                      reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
+  if (end) {
+    GM_ENV_SYNC();   // lane 0's epilogue writes (RNG, counters) before every lane reads them
+    const GmResetKeep keep{S.s.rng, S.s.old_x, S.s.old_y, S.s.old_z, S.s.episode + 1, S.s.newton_caps};
+    GM_ENV_SYNC();   // every lane has read what survives before the image is cleared
+    static_assert(sizeof(S.st) >= sizeof(uint16_t) * (GM_SPAWN_MAX_XY + GM_SPAWN_MAX_ROT), "spawn buffers fit the union");
+    uint16_t* sh_pxy = reinterpret_cast<uint16_t*>(&S.st);
+    reset_env(S.s, *g, keep, m, C, T, J.eq, nullptr, J.objs, J.n_objects, env, J.scene, J.scene_tries, J.sr,
+              sh_pxy, sh_pxy + GM_SPAWN_MAX_XY, lane);
+    get_obs_lanes(S.s, g->ring, C, obs + (size_t)env * C->n_obs, lane);
+  }
+}
+// Finish the job after its last env-step (k_end = J.steps): the actor-critic's last value
+template <int CL>
+__device__ __forceinline__ void rollout_finish(SharedT<CL>& S, GmEnvState* g, float* __restrict__ obs, int env,
+                                               int n_envs, const GmRolloutJob& J, int k_end, const gm_model* __restrict__ m,
+                                               const gm_config* __restrict__ C, int lane) {
+  if (J.driver == GM_DRV_AC)
+    ac_rollout_driver(2, J.ac, obs + (size_t)env * C->n_obs, env, n_envs, k_end, J.max_ep, rollout_gid(J, env),
+                      reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
+}
+
 // the persistent loop of gm_step_kernel's chunked mode (a mode of the one kernel, not a
-// kernel of its own: substep_loop keeps its single caller and so its constant LDS base)
+// kernel of its own: substep_loop keeps its single caller and so its constant LDS base): take
+// work; load state and carry; per env-step actions, substeps, epilogue, end; finish or yield
 template <int CL, bool DUO>
 __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __restrict__ states,
                                                   const gm_model* __restrict__ m, const gm_config* __restrict__ C,
@@ -2766,255 +2668,94 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
                                                   float* __restrict__ rew, uint8_t* __restrict__ done, int n_envs,
                                                   const int32_t* __restrict__ order, uint32_t* __restrict__ cost,
                                                   const GmChunkQ& q, int lane) {
-  int xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  xcc &= 7;
-  uint32_t* bq = q.ctr + xcc * GM_CQ_NB * 32;                    // this XCD's bucket counters
-  uint64_t* ring = q.ring + (size_t)xcc * GM_CQ_NB * q.cap;      // and rings
-  uint32_t* fresh_head = q.ctr + GM_CQ_FRESH;
-  uint32_t* n_done = q.ctr + GM_CQ_DONE;
-  const uint32_t n = (uint32_t)n_envs;
-  // bucket scale: the heaviest env's last cost + 1, snapshot by gm_dispatch_order_kernel, so
-  // every wave of the launch buckets alike (costs of this launch go to the second half)
-  // (costs are per env-step: a job of q.steps env-steps is predicted at q.steps times its env's)
-  const uint32_t cmax = q.ctr[GM_CQ_CMAX] * (uint32_t)(q.steps > 1 ? q.steps : 1);
+  GmCqWave w = cq_wave(q, n_envs);
+  const GmRolloutJob& J = q.job;
   unsigned long long busy = 0, poll = 0, last_end = 0;
-  bool first = true, saw_empty = false;
+  bool first = true;
   for (;;) {
     if (q.prio > 0) __builtin_amdgcn_s_setprio(0);   // looking for work: the partner wave first
     const unsigned long long tw = __builtin_amdgcn_s_memrealtime();
-    // take work (lane 0): a continuation queued on this XCD first, else a fresh env in
-    // cost order; -1 once every env has finished its env-step
-    int pick = -1, fresh = 0;
-    for (;;) {
-      // bucket occupancy, one lane per bucket; the highest non-empty bucket is the best
-      // yielded env (its exact work left rides in the entry; an entry still in flight
-      // reads 0 and counts as large)
-      uint32_t hb = 0, tb = 0;
-      if (lane < GM_CQ_NB) { hb = ld_agent(bq + lane * 32); tb = ld_agent(bq + lane * 32 + 1); }
-      const unsigned long long ne = __ballot(lane < GM_CQ_NB && hb < tb);
-      const uint32_t fh = __builtin_amdgcn_readfirstlane(ld_agent(fresh_head));
-      const bool have_f = fh < n;
-      if (!have_f && !saw_empty) {
-        saw_empty = true;
-        if (lane == 0)
-          __hip_atomic_fetch_min(q.st + 1, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      const int bsel = ne ? 63 - __builtin_clzll(ne) : -1;
-      bool take_c = bsel >= 0;
-      if (take_c && have_f) {
-        const uint32_t h = __builtin_amdgcn_readlane(hb, bsel);
-        const uint64_t e = ld_agent64(ring + (size_t)bsel * q.cap + h % (uint32_t)q.cap);
-        take_c = e == 0ull || (uint64_t)(uint32_t)(e >> 32) >= (uint64_t)cost[order[fh]] * (uint64_t)(q.steps > 1 ? q.steps : 1);
-      }
-      if (take_c) {
-        int got = 0;
-        if (lane == 0) {
-          uint64_t* rb = ring + (size_t)bsel * q.cap;
-          const int64_t c = claim_bucket(bq + bsel * 32);
-          if (c >= 0) {
-            got = 1;
-            const uint32_t i = (uint32_t)c % (uint32_t)q.cap;
-            uint64_t v;
-            uint32_t polls = 0;
-            // acquire: pairs with the producer's release store of this entry
-            while ((v = __hip_atomic_load(rb + i, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) == 0ull &&
-                   ld_agent(n_done) < n) {
-              __builtin_amdgcn_s_sleep(2);
-              polls++;
-            }
-            if (polls) { add_agent(q.ctr + GM_CQ_DONE + 5, 1u); add_agent(q.ctr + GM_CQ_DONE + 6, polls); }
-            if (v != 0ull) {
-              st_agent(rb + i, 0ull);
-              add_agent(q.ctr + GM_CQ_DONE + 2, 1u);
-              pick = (int)(uint32_t)v - 1;
-            }
-          }
-        }
-        if (__builtin_amdgcn_readfirstlane(got)) break;   // pick < 0: everything finished while waiting
-        continue;                                          // the entry went to another wave: poll again
-      }
-      if (have_f) {
-        if (lane == 0) {
-          const uint32_t i = add_agent(fresh_head, 1u);
-          if (i < n) { pick = order[i]; fresh = 1; }
-        }
-        if (__builtin_amdgcn_readfirstlane(pick) >= 0) break;
-      } else if (q.steal) {
-        // nothing unstarted and nothing yielded on this XCD: the best yielded env of another
-        // XCD (its hot state was published with an agent-scope release, the acquire below
-        // makes it visible here; same-XCD resumption is only the faster case).  Lane l looks
-        // at XCD l / 8, buckets 15 - l % 8 and 7 - l % 8.
-        const int x2 = lane >> 3;
-        const uint32_t* bq2 = q.ctr + x2 * GM_CQ_NB * 32;
-        const int bh = 15 - (lane & 7), bl = 7 - (lane & 7);
-        const bool other = x2 != xcc;
-        const bool nh = other && ld_agent(bq2 + bh * 32) < ld_agent(bq2 + bh * 32 + 1);
-        const bool nl = other && ld_agent(bq2 + bl * 32) < ld_agent(bq2 + bl * 32 + 1);
-        const unsigned long long mh = __ballot(nh), ml = __ballot(nl);
-        if (mh | ml) {
-          // the highest non-empty bucket over the other XCDs (lowest lane among equals)
-          int src = -1, sb = -1;
-          for (int r = 0; r < 8 && src < 0; r++) {   // bucket 15 - r in the high half, lanes with lane % 8 == r
-            const unsigned long long m8 = mh & (0x0101010101010101ull << r);
-            if (m8) { src = (int)__builtin_ctzll(m8) >> 3; sb = 15 - r; }
-          }
-          for (int r = 0; r < 8 && src < 0; r++) {
-            const unsigned long long m8 = ml & (0x0101010101010101ull << r);
-            if (m8) { src = (int)__builtin_ctzll(m8) >> 3; sb = 7 - r; }
-          }
-          int got = 0;
-          if (lane == 0) {
-            uint32_t* sbq = q.ctr + src * GM_CQ_NB * 32;
-            uint64_t* rb = q.ring + (size_t)src * GM_CQ_NB * q.cap + (size_t)sb * q.cap;
-            const int64_t c = claim_bucket(sbq + sb * 32);
-            if (c >= 0) {
-              got = 1;
-              const uint32_t i = (uint32_t)c % (uint32_t)q.cap;
-              uint64_t v;
-              uint32_t polls = 0;
-              while ((v = __hip_atomic_load(rb + i, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) == 0ull &&
-                     ld_agent(n_done) < n) {
-                __builtin_amdgcn_s_sleep(2);
-                polls++;
-              }
-              if (polls) { add_agent(q.ctr + GM_CQ_DONE + 5, 1u); add_agent(q.ctr + GM_CQ_DONE + 6, polls); }
-              if (v != 0ull) {
-                st_agent(rb + i, 0ull);
-                add_agent(q.ctr + GM_CQ_DONE + 2, 1u);
-                add_agent(q.ctr + GM_CQ_DONE + 4, 1u);   // steals
-                pick = (int)(uint32_t)v - 1;
-              }
-            }
-          }
-          if (__builtin_amdgcn_readfirstlane(got)) break;   // pick < 0: everything finished while waiting
-        }
-      }
-      if (__builtin_amdgcn_readfirstlane(ld_agent(n_done)) >= n) break;
-      __builtin_amdgcn_s_sleep(2);
-    }
-    pick = __builtin_amdgcn_readfirstlane(pick);
-    fresh = __builtin_amdgcn_readfirstlane(fresh);
+    const GmCqPick pick = cq_take_work(q, w, order, cost, lane);
     const unsigned long long tp = __builtin_amdgcn_s_memrealtime();
     poll += tp - tw;
-    if (pick < 0) break;
+    if (pick.env < 0) break;
     if (first && lane == 0)
-      __hip_atomic_fetch_min(q.st, tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_min(q.st + GM_CQT_FIRST_PICK, tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     first = false;
-    const int env = pick;
-    uint64_t* env_t = reinterpret_cast<uint64_t*>(q.st) + 16 + gridDim.x + 2 * (size_t)env;   // gm_chunk_timeline
-    if (fresh && lane == 0) st_agent(env_t, tp);
+    const int env = pick.env;
+    uint64_t* env_t = reinterpret_cast<uint64_t*>(q.st) + cq_time_of_env(gridDim.x, env);
+    if (pick.fresh && lane == 0) st_agent(env_t, tp);
     const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-    if (!fresh) {
-      // lane 0's acquire load saw the entry; the fence extends that acquire to the whole
-      // wave's loads of the env's state (another CU of this XCD stored it) below
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
+    // lane 0's acquire load saw the entry: extend it to the whole wave's loads of the state
+    if (!pick.fresh) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     GmEnvState* g = states + env;
     load_state(S, g, lane);
     GmChunkCarry cr;
-    if (fresh) {
+    if (pick.fresh) {
       cr.sub_done = 0;
       cr.nsub = C->sim_steps_per_action + S.s.extra_substeps;
       cr.work_nefc = 0; cr.work_mpr = 0; cr.work_newton = 0; cr.stp_fixed = 0;
-      cr.clk = 0;
-      cr.yielded = 0;
-      cr.steps_left = q.steps;
-      cr.step_idx = 0;
-      cr.job_yields = 0;
+      cr.clk = 0; cr.yielded = 0; cr.step_idx = 0; cr.job_yields = 0;
+      cr.steps_left = J.steps;
     } else {
       // agent-scope loads: never served by a scalar cache that the acquire does not reach
       const uint32_t* src = reinterpret_cast<const uint32_t*>(q.carry + env);
       uint32_t* dst = reinterpret_cast<uint32_t*>(&cr);
 #pragma unroll
-      for (int w = 0; w < (int)(sizeof(GmChunkCarry) / 4); w++) dst[w] = ld_agent(src + w);
+      for (int i = 0; i < (int)(sizeof(GmChunkCarry) / 4); i++) dst[i] = ld_agent(src + i);
     }
     if (lane == 0) {
       S.work_nefc = cr.work_nefc; S.work_mpr = cr.work_mpr; S.work_newton = cr.work_newton;
       S.stp_fixed = cr.stp_fixed;
     }
     GM_ENV_SYNC();
-    const uint64_t own = (uint64_t)cost[env] * (uint64_t)(q.steps > 1 ? q.steps : 1);   // the job's predicted cost
+    const uint64_t own = (uint64_t)cost[env] * (uint64_t)cq_job_scale(q);   // the job's predicted cost
+    const uint32_t est = (uint32_t)(own > 0xFFFFFFFFull ? 0xFFFFFFFFull : own);
     const int s_nom = C->sim_steps_per_action;
     bool finished = false;
     for (;;) {   // the env-steps of this pick
-      if (cr.sub_done == 0 && q.act_mode >= 0) {
-        // a new env-step of a rollout: the driver's actions first (they may add the
-        // termination lift's substeps), as gm_set_action before gm_step
-        if (q.act_mode == 2) {
-          // gm_policy_act on this env alone: select_action from its current observation,
-          // then set_discrete_action (the LDS scratch: the dynamics union, dead between
-          // env-steps)
+      if (cr.sub_done == 0 && J.driver >= 0) {
+        // begin an env-step of a rollout: the driver's actions, applied as gm_set_action /
+        // gm_set_discrete_action before gm_step (they may add the termination lift's substeps)
+        const float* o = obs + (size_t)env * C->n_obs;
+        if (J.driver == GM_DRV_DQN) {
           static_assert(sizeof(S.st) >= sizeof(float) * 2 * GP_ROW, "policy activations fit the union");
-          const int a = gp_select_one(obs + (size_t)env * C->n_obs, q.pparams, q.pnet, q.peps[cr.step_idx], q.pseed,
-                                      q.pdecision + (uint64_t)cr.step_idx, (uint64_t)(q.sr.env_offset + env),
+          const int a = gp_select_one(o, J.pparams, J.pnet, J.peps[cr.step_idx], J.seed,
+                                      J.pdecision + (uint64_t)cr.step_idx, (uint64_t)rollout_gid(J, env),
                                       reinterpret_cast<float*>(&S.st), lane);
           if (lane == 0) {
             set_action_one(S.s, m, C, a, 0.0f);
             S.stp_fixed = 0;
           }
-        } else if (q.act_mode == 5) {
+        } else if (J.driver == GM_DRV_AC) {
           static_assert(sizeof(S.st) >= sizeof(float) * GA_ONE_FLOATS, "actor-critic activations fit the union");
-          ac_rollout_driver(0, q.ac, obs + (size_t)env * C->n_obs, env, n_envs, cr.step_idx, q.max_ep,
-                            q.sr.env_offset + env, reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
+          ac_rollout_driver(0, J.ac, o, env, n_envs, cr.step_idx, J.max_ep, rollout_gid(J, env),
+                            reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
           if (lane == 0) S.stp_fixed = 0;
         } else if (lane == 0) {
-          driver_actions(S.s, g->ring, m, C, q.act_mode, q.act_seed, q.jitter, q.sr.env_offset + env);
+          driver_actions(S.s, g->ring, m, C, J.driver, J.seed, J.jitter, rollout_gid(J, env));
           S.stp_fixed = 0;
         }
         GM_ENV_SYNC();
         cr.nsub = C->sim_steps_per_action + S.s.extra_substeps;
       }
-      // run to the end of the env-step unless an unstarted env has become the longer job
-      // (work left counted over the launch's whole job of env-steps)
-      const int left = cr.nsub - cr.sub_done;
-      const int job_left = (cr.steps_left - 1) * s_nom + left;
-      const int job_total = q.steps > 1 ? q.steps * s_nom : cr.nsub;
-      const uint32_t est = (uint32_t)(own > 0xFFFFFFFFull ? 0xFFFFFFFFull : own);
-      const GmPreempt pre{fresh_head, order, cost, n, est, job_left, job_total,
-                          cr.yielded < q.max_yields ? q.chunk : 0, q.margin, bq, cmax, q.cmargin, q.prio,
-                          q.steps > 1 ? q.steps : 1};
-      job_prio((uint64_t)est * (uint64_t)job_left / (uint64_t)(job_total > 0 ? job_total : 1), cmax, q.prio);
-      const int k = substep_loop<CL, false, false, DUO>((GM_AS_LDS SharedT<CL>*)&S, (const GM_AS_GLOBAL gm_model*)m,
-                                            (const GM_AS_GLOBAL GmTopo*)T, (const GM_AS_GLOBAL gm_config*)C, lane,
-                                            false, left, false, pre);
-      cr.sub_done += k;
+      // run to the end of the env-step unless another env has become the longer job (whole jobs)
+      const int job_left = cq_job_left(cr, s_nom), job_total = cq_job_total(q, cr, s_nom);
+      const GmPreempt pre{cq_counter(q, GM_CQC_FRESH), order, cost, w.n, est, job_left, job_total,
+                          cr.yielded < q.max_yields ? q.chunk : 0, q.margin, w.bq, w.cmax, q.cmargin, q.prio,
+                          cq_job_scale(q)};
+      job_prio((uint64_t)est * (uint64_t)job_left / (uint64_t)(job_total > 0 ? job_total : 1), w.cmax, q.prio);
+      cr.sub_done += substep_loop<CL, false, false, DUO>(
+          (GM_AS_LDS SharedT<CL>*)&S, (const GM_AS_GLOBAL gm_model*)m, (const GM_AS_GLOBAL GmTopo*)T,
+          (const GM_AS_GLOBAL gm_config*)C, lane, false, cr.nsub - cr.sub_done, false, pre);
       if (cr.sub_done < cr.nsub) break;   // yielded
       unsigned long long t0 = 0;
       env_step_epilogue(S, m, C, T, obs, rew, done, env, lane, false, t0);
-      if (q.act_mode >= 0) {
-        // gm_autoreset_episodes on this env: the episode-end record, then MjEnv.reset
-        const int r = __builtin_amdgcn_readfirstlane(
-            (S.s.done || (q.max_ep > 0 && S.s.num_action_steps >= q.max_ep)) ? 1 : 0);
-        if (lane == 0 && q.rec) {
-          gm_episode_end e;
-          e.ret = r ? S.s.cumulative_reward : __builtin_nanf("");
-          e.length = r ? S.s.num_action_steps : 0;
-          e.success = (r && S.s.bev_last[GM_EV_successful_grasp]) ? 1 : 0;
-          e.pad[0] = e.pad[1] = e.pad[2] = 0;
-          q.rec[(size_t)cr.step_idx * n + env] = e;
-        }
-        if (q.act_mode == 5)
-          ac_rollout_driver(1, q.ac, obs + (size_t)env * C->n_obs, env, n_envs, cr.step_idx, q.max_ep,
-                            q.sr.env_offset + env, reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
-        if (r) {
-          GM_ENV_SYNC();   // lane 0's epilogue writes (RNG, counters) before every lane reads them
-          const GmResetKeep keep{S.s.rng, S.s.old_x, S.s.old_y, S.s.old_z, S.s.episode + 1, S.s.newton_caps};
-          GM_ENV_SYNC();   // every lane has read what survives before the image is cleared
-          static_assert(sizeof(S.st) >= sizeof(uint16_t) * (GM_SPAWN_MAX_XY + GM_SPAWN_MAX_ROT),
-                        "spawn search buffers alias the (dead between env-steps) dynamics union");
-          uint16_t* sh_pxy = reinterpret_cast<uint16_t*>(&S.st);
-          reset_env(S.s, *g, keep, m, C, T, q.eq, nullptr, q.objs, q.n_objects, env, q.scene, q.scene_tries, q.sr,
-                    sh_pxy, sh_pxy + GM_SPAWN_MAX_XY, lane);
-          get_obs_lanes(S.s, g->ring, C, obs + (size_t)env * C->n_obs, lane);
-        }
-      }
+      rollout_end_step(S, g, obs, env, n_envs, J, cr.step_idx, m, C, T, lane);
       cr.steps_left -= 1;
       cr.step_idx += 1;
       if (cr.steps_left <= 0) {
-        if (q.act_mode == 5)
-          ac_rollout_driver(2, q.ac, obs + (size_t)env * C->n_obs, env, n_envs, cr.step_idx, q.max_ep,
-                            q.sr.env_offset + env, reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
+        rollout_finish(S, g, obs, env, n_envs, J, cr.step_idx, m, C, lane);
         finished = true;
         break;
       }
@@ -3024,22 +2765,18 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
     }
     if (finished) {
       if (cost && lane == 0) {
-        // the dispatch cost (see gm_step_kernel): clocks of this job's chunks, blended with
-        // the work model
-        const uint32_t now = cr.clk + (uint32_t)((__builtin_amdgcn_s_memtime() - t_start) >> 6);
-        const uint32_t model = 14000u * (uint32_t)q.steps + 19u * (uint32_t)S.work_nefc + 188u * (uint32_t)S.work_mpr +
-                               940u * (uint32_t)S.work_newton;
-        // recorded for the next launch's order, per env-step (whatever the next launch's job length)
-        cost[n + env] = ((now >> 1) + (model >> 1)) / (uint32_t)(q.steps > 1 ? q.steps : 1);
+        const uint32_t clk = cr.clk + (uint32_t)((__builtin_amdgcn_s_memtime() - t_start) >> 6);
+        // for the next launch's order, per env-step (whatever its job length)
+        cost[w.n + env] = dispatch_cost(clk, (uint32_t)cq_job_scale(q), S.work_nefc, S.work_mpr, S.work_newton);
         // diagnostics (gm_chunk_job_stats): the job's busy clocks / 64 and its yields
-        __hip_atomic_store(&q.carry[env].clk, now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&q.carry[env].clk, clk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&q.carry[env].job_yields, cr.job_yields, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       store_state(S, g, lane);
       if (lane == 0) {
-        add_agent(n_done, 1u);
+        add_agent(cq_counter(q, GM_CQC_DONE), 1u);
         st_agent(env_t + 1, __builtin_amdgcn_s_memrealtime());
-        __hip_atomic_fetch_max(q.st + 2, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
+        __hip_atomic_fetch_max(q.st + GM_CQT_LAST_DONE, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
       }
     } else {
@@ -3047,40 +2784,21 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
       if (lane == 0) {
         cr.work_nefc = S.work_nefc; cr.work_mpr = S.work_mpr; cr.work_newton = S.work_newton;
         cr.stp_fixed = S.stp_fixed;
-        cr.yielded += 1;
-        cr.job_yields += 1;
+        cr.yielded += 1; cr.job_yields += 1;
         cr.clk += (uint32_t)((__builtin_amdgcn_s_memtime() - t_start) >> 6);
         q.carry[env] = cr;
       }
-      // publish (MI355X_MICROARCH.md, inter-workgroup visibility, valid forms): the wave's
-      // state / carry stores drained, then lane 0's agent-scope release (the XCD L2 written
-      // back, so a consumer on ANY XCD sees the bytes after its acquire), drained again
-      // before the ring entry's relaxed agent store
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      GM_ENV_SYNC();
-      if (lane == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int job_total = q.steps > 1 ? q.steps * s_nom : cr.nsub;
-        const int job_left = (cr.steps_left - 1) * s_nom + (cr.nsub - cr.sub_done);
-        const uint64_t rem = own * (uint64_t)job_left / (uint64_t)job_total;
-        add_agent(q.ctr + GM_CQ_DONE + 1, 1u);
-        const uint32_t b = rem * GM_CQ_NB / cmax < GM_CQ_NB - 1 ? (uint32_t)(rem * GM_CQ_NB / cmax) : GM_CQ_NB - 1;
-        const uint32_t t = add_agent(bq + b * 32 + 1, 1u) % (uint32_t)q.cap;
-        __hip_atomic_store(ring + (size_t)b * q.cap + t,
-                           ((rem > 0xFFFFFFFFull ? 0xFFFFFFFFull : rem) << 32) | ((uint64_t)env + 1u), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      }
+      cq_publish_yield(q, w, own, cq_job_left(cr, s_nom), cq_job_total(q, cr, s_nom), env, lane);
     }
     GM_ENV_SYNC();   // LDS image reused by the next pick
     last_end = __builtin_amdgcn_s_memrealtime();
     busy += last_end - tp;
   }
   if (lane == 0) {
-    __hip_atomic_fetch_add(q.st + 3, busy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(q.st + 4, poll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(q.st + GM_CQT_BUSY, busy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(q.st + GM_CQT_POLL, poll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // this workgroup's last work (gm_chunk_timeline), its XCD in the top four bits
-    st_agent(reinterpret_cast<uint64_t*>(q.st) + 16 + blockIdx.x, last_end | ((uint64_t)xcc << 60));
+    st_agent(reinterpret_cast<uint64_t*>(q.st) + cq_time_of_wave(blockIdx.x), last_end | ((uint64_t)w.xcc << 60));
   }
 }
 // mode 0: action_step + obs/done/reward; mode 1: calibrate_reset settle (400 substeps,
@@ -3226,18 +2944,9 @@ __device__ __forceinline__ void step_kernel_body(SharedT<CL>& S,
     GM_ENV_SYNC();
     if (lane < GM_NPHASE) dbg.phase[(size_t)env * GM_NPHASE + lane] = S.tph[lane];
   }
-  if (cost && lane == 0) {
-    // next env-step's dispatch cost: the measured one (shader clocks / 64; it carries
-    // co-residency noise) averaged with a work model of this env-step (a fixed part, the
-    // Hessian work per constraint row, each Newton iteration, the convex collider's
-    // latency per substep that ran it; fitted on the C3 workload, tools/tail_bench.py): the blend orders the
-    // next launch closer to its true costs than either alone (LPT makespan 1.17 vs 1.21
-    // of the ideal on recorded costs)
-    const uint32_t now = (uint32_t)((__builtin_amdgcn_s_memtime() - t_start) >> 6);
-    const uint32_t model = 14000u + 19u * (uint32_t)S.work_nefc + 188u * (uint32_t)S.work_mpr +
-                           940u * (uint32_t)S.work_newton;
-    cost[n_envs + env] = (now >> 1) + (model >> 1);   // recorded for the next launch's order
-  }
+  if (cost && lane == 0)   // recorded for the next launch's order
+    cost[n_envs + env] = dispatch_cost((uint32_t)((__builtin_amdgcn_s_memtime() - t_start) >> 6), 1u, S.work_nefc,
+                                       S.work_mpr, S.work_newton);
   store_state(S, states + env, lane);
 }
 template <int CL, bool CAL, bool DUO = false>
@@ -3275,13 +2984,13 @@ extern "C" __global__ __launch_bounds__(1024) void gm_dispatch_order_kernel(uint
   __shared__ uint32_t cnt[256];
   __shared__ uint32_t cmax;
   const int t = threadIdx.x;
-  if (chunk_ctr && t < 39) chunk_ctr[GM_CQ_LAST + t] = chunk_ctr[GM_CQ_FRESH + t];   // last launch's, for diagnostics
+  if (chunk_ctr && t < GM_CQC_N) chunk_ctr[GM_CQ_LAST + t] = chunk_ctr[GM_CQ_FRESH + t];   // last launch's, for diagnostics
   __syncthreads();
   if (chunk_ctr)
     for (int w = t; w < GM_CQ_WORDS; w += 1024) chunk_ctr[w] = 0;   // the chunked launch's queue counters
-  if (chunk_st && t < 8) {
-    chunk_st[8 + t] = chunk_st[t];
-    chunk_st[t] = (t < 2) ? ~0ull : 0ull;
+  if (chunk_st && t < GM_CQT_LAST) {
+    chunk_st[GM_CQT_LAST + t] = chunk_st[t];
+    chunk_st[t] = (t == GM_CQT_FIRST_PICK || t == GM_CQT_FIRST_EMPTY) ? ~0ull : 0ull;   // (fetch_min targets)
   }
   if (t < 256) cnt[t] = 0;
   if (t == 0) cmax = 1;
@@ -3295,7 +3004,7 @@ extern "C" __global__ __launch_bounds__(1024) void gm_dispatch_order_kernel(uint
   atomicMax(&cmax, m);
   __syncthreads();
   const uint64_t cm = (uint64_t)cmax + 1;
-  if (chunk_ctr && t == 0) chunk_ctr[GM_CQ_CMAX] = (uint32_t)cm;
+  if (chunk_ctr && t == 0) chunk_ctr[GM_CQ_FRESH + GM_CQC_CMAX] = (uint32_t)cm;
   for (int i = t; i < n; i += 1024) {
     const int b = 255 - (int)(((uint64_t)cost[i] * 256) / cm);
     atomicAdd(&cnt[b], 1u);
@@ -3737,20 +3446,12 @@ extern "C" __global__ void gm_autoreset_mask_kernel(const GmEnvState* __restrict
   int env = blockIdx.x * blockDim.x + threadIdx.x;
   if (env >= n_envs) return;
   const GmEnvState& s = states[env];
-  uint8_t r = (done[env] || (max_steps > 0 && s.num_action_steps >= max_steps)) ? 1 : 0;
-  mask[env] = r;
-  const float ret = r ? s.cumulative_reward : __builtin_nanf("");
-  if (returns) returns[env] = ret;
-  if (episodes) {
-    // successful_grasp (mjclass.cpp:1295-1322): this env-step's event value, which
-    // update_events leaves in bev_last
-    gm_episode_end e;
-    e.ret = ret;
-    e.length = r ? s.num_action_steps : 0;
-    e.success = (r && s.bev_last[GM_EV_successful_grasp]) ? 1 : 0;
-    e.pad[0] = e.pad[1] = e.pad[2] = 0;
-    episodes[env] = e;
-  }
+  const int end = gm_episode_end_code(done[env], s.num_action_steps, max_steps);
+  mask[env] = end ? 1 : 0;
+  const gm_episode_end e = gm_episode_end_record(end, s.cumulative_reward, s.num_action_steps,
+                                                 s.bev_last[GM_EV_successful_grasp]);
+  if (returns) returns[env] = e.ret;
+  if (episodes) episodes[env] = e;
 }
 #endif
 

@@ -295,6 +295,30 @@ int gm_program_episode(uint64_t seed, int64_t gid, int32_t ep) {
   return gm_spawn_int(seed, gid, ep, 21, 0, 3) == 0;
 }
 
+// The episode-end rule (gm_autoreset_episodes, the rollouts' auto-reset, the actor-critic's
+// record): 0 the episode goes on, 1 terminal (done), 2 truncated; nonzero resets the env
+static inline
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+int gm_episode_end_code(int done, int32_t num_action_steps, int max_ep) {
+  return done ? 1 : (max_ep > 0 && num_action_steps >= max_ep) ? 2 : 0;
+}
+// the record of an env-step with that end code.  successful_grasp (mjclass.cpp:1295-1322): this
+// env-step's event value, which update_events leaves in bev_last
+static inline
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+gm_episode_end gm_episode_end_record(int end, float cumulative_reward, int32_t num_action_steps, int32_t successful_grasp) {
+  gm_episode_end e;
+  e.ret = end ? cumulative_reward : __builtin_nanf("");
+  e.length = end ? num_action_steps : 0;
+  e.success = (end && successful_grasp) ? 1 : 0;
+  e.pad[0] = e.pad[1] = e.pad[2] = 0;
+  return e;
+}
+
 // Topology derived from gm_model on the host (the canonical gripper tree):
 // dof/body of chain position p in finger chain f is first + p - 1 (p >= 1),
 // position 0 of every finger / palm chain is the base dof.

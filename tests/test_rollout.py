@@ -23,6 +23,9 @@ N, K, MAX_EP, SEED = 96, 14, 6, 77
 # (on 24 workgroups: with a wave slot per env nothing would ever wait in the queue)
 HANDOFF = {"GM_CHUNK_SUBSTEPS": "1", "GM_CHUNK_MARGIN": "0", "GM_CHUNK_YIELDS": "60", "GM_CHUNK_CMARGIN": "0",
            "GM_CHUNK_GRID": "24"}
+# the same with cross-XCD resumption off: every yielded env is claimed on the XCD that queued it
+NO_STEAL = dict(HANDOFF, GM_CHUNK_STEAL="0")
+DISPATCH = {"default": None, "handoff-heavy": HANDOFF, "handoff-no-steal": NO_STEAL}
 
 
 def make_env(gm, env_vars=None, n=N):
@@ -70,7 +73,7 @@ def snapshot(env, records):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode,dispatch", [(0, "default"), (1, "default"), (0, "handoff-heavy"), (3, "default"),
-                                           (4, "handoff-heavy")])
+                                           (4, "handoff-heavy"), (0, "handoff-no-steal")])
 def test_rollout_equals_per_step_api(gm, mode, dispatch):
     if not gpu_available():
         pytest.skip("no GPU")
@@ -79,12 +82,12 @@ def test_rollout_equals_per_step_api(gm, mode, dispatch):
     ra = torch.zeros((K, N, 3), dtype=torch.int32, device="cuda")
     rb = torch.zeros((K, N, 3), dtype=torch.int32, device="cuda")
     a = make_env(gm)
-    b = make_env(gm, HANDOFF if dispatch == "handoff-heavy" else None)
+    b = make_env(gm, DISPATCH[dispatch])
     try:
         per_step(gm, a, mode, ra)
         # (the hand-off test needs dispatch costs, which a context records from its first
         # env-step on: b takes that one through the per-step API too)
-        k0 = 1 if dispatch == "handoff-heavy" else 0
+        k0 = 0 if dispatch == "default" else 1
         per_step(gm, b, mode, rb, steps=k0)
         b.rollout(K - k0, action_mode=mode, seed=SEED, jitter=0.2, max_episode_steps=MAX_EP,
                   records_dev_ptr=rb[k0:].data_ptr())
@@ -101,11 +104,14 @@ def test_rollout_equals_per_step_api(gm, mode, dispatch):
         _, length, _ = unpack_episodes(torch.from_numpy(sa[5].reshape(-1, 3)))
         assert int((length > 0).sum()) >= N, int((length > 0).sum())
         assert int(va["episode"].min()) >= 2
-        if dispatch == "handoff-heavy":
+        if dispatch != "default":
             st = b.chunk_stats()
             assert st["yields"] > N, st
-            # idle waves resumed yielded envs of other XCDs (cross-XCD hand-offs)
-            assert st["steals"] > 0, st
+            if dispatch == "handoff-heavy":
+                # idle waves resumed yielded envs of other XCDs (cross-XCD hand-offs)
+                assert st["steals"] > 0, st
+            else:
+                assert st["steals"] == 0, st
     finally:
         a.close()
         b.close()

@@ -18,7 +18,8 @@ import tempfile
 
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-FUNCS = ("ac_rollout_driver", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel", "gm_policy_kernel")
+FUNCS = ("ac_rollout_driver", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel", "gm_policy_kernel",
+         "substep_loop", "reset_env", "driver_actions")
 
 
 def tool(name, *args):
@@ -49,7 +50,10 @@ def usage(obj):
         kernels[short] = dict(vgpr=int(g("vgpr_count")), sgpr=int(g("sgpr_count")),
                               lds_bytes=int(g("group_segment_fixed_size")),
                               scratch_bytes_per_lane=int(g("private_segment_fixed_size")), code_bytes=size.get(name))
-    funcs = {f: n for s, n in size.items() for f in FUNCS if f in s}
+    funcs = {}
+    for f in FUNCS:   # a template's instantiations go by their symbols
+        hits = {s: n for s, n in size.items() if f in s}
+        funcs.update({f: n for n in hits.values()} if len(hits) == 1 else hits)
     return dict(kernels=kernels, functions=funcs)
 
 
