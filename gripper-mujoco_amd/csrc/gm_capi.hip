@@ -31,6 +31,37 @@ hipError_t gm_cal_launch_read(hipStream_t st, const GmEnvState* states, uint8_t*
 hipError_t gm_cal_launch_gauge(int n_seg, hipStream_t st, const GmEnvState* states, const gm_model* m, const GmTopo* T,
                                int env, float* out);
 
+// Move-only owner of one hipMalloc allocation of T (Pinned: of one hipHostMalloc allocation): the
+// only code of this file that allocates or frees device or pinned memory.  It reads as the raw
+// pointer wherever one is expected; a copy of that pointer is a view and frees nothing.
+template <class T, bool Pinned = false>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  // n elements, uninitialised; what the owner held before is released first
+  hipError_t alloc(size_t n) {
+    reset();
+    return Pinned ? hipHostMalloc(&p_, sizeof(T) * n, hipHostMallocDefault) : hipMalloc(&p_, sizeof(T) * n);
+  }
+  void reset() {
+    if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));   // (hipFree synchronises the whole device)
+    p_ = nullptr;
+  }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+};
+template <class T>
+using HostBuf = DevBuf<T, true>;
+
 struct gm_ctx {
   int device = 0;
   int n_envs = 0;
@@ -44,47 +75,48 @@ struct gm_ctx {
   gm_model model;
   gm_config cfg;
   GmTopo topo;
-  // device buffers
-  GmEnvState* d_state = nullptr;
-  gm_model* d_model = nullptr;
-  gm_config* d_cfg = nullptr;
-  GmTopo* d_topo = nullptr;
-  gm_object* d_objs = nullptr;
-  double* d_eq = nullptr;
-  float* d_obs = nullptr;              // d_obs, d_rew, d_done: one allocation (d_out), read back
-  float* d_rew = nullptr;              // by gm_get_outputs in one copy through h_out (pinned)
-  uint8_t* d_done = nullptr;
-  void* d_out = nullptr;
-  void* h_out = nullptr;
+  // device buffers: every DevBuf / HostBuf is released with the context (gm_destroy, after
+  // its last synchronise); the raw pointers among them are views
+  DevBuf<GmEnvState> d_state;
+  DevBuf<gm_model> d_model;
+  DevBuf<gm_config> d_cfg;
+  DevBuf<GmTopo> d_topo;
+  DevBuf<gm_object> d_objs;
+  DevBuf<double> d_eq;
+  float* d_obs = nullptr;              // d_obs, d_rew, d_done: views into one allocation (d_out),
+  float* d_rew = nullptr;              // read back by gm_get_outputs in one copy through h_out
+  uint8_t* d_done = nullptr;           // (pinned)
+  DevBuf<char> d_out;
+  HostBuf<char> h_out;
   size_t out_bytes = 0;
-  float* d_act = nullptr;
+  DevBuf<float> d_act;
   // host actions are staged through a pinned buffer so gm_set_action / gm_set_discrete_action
   // return without a stream synchronisation (stage_ev: the previous staging copy is done)
-  void* h_stage = nullptr;
+  HostBuf<char> h_stage;
   size_t stage_bytes = 0;
   hipEvent_t stage_ev = nullptr;
-  int32_t* d_dact = nullptr;
-  uint8_t* d_mask = nullptr;
+  DevBuf<int32_t> d_dact;
+  DevBuf<uint8_t> d_mask;
   // scratch of the force-measurement calls (gm_set_motor_target's targets and flags,
-  // gm_get_sensor_si's readings): allocated once with the context, no per-call hipMalloc /
-  // hipFree (a hipFree synchronises the whole device)
-  void* d_scratch = nullptr;
-  gm_spawn* d_spawn = nullptr;
-  int32_t* d_order = nullptr;          // workgroup -> env dispatch order (cost-sorted)
-  uint32_t* d_cost = nullptr;          // per-env cost of the last env-step (clocks / 64)
+  // gm_get_sensor_si's readings): allocated once with the context, no per-call allocation
+  // (freeing one synchronises the whole device)
+  DevBuf<char> d_scratch;
+  DevBuf<gm_spawn> d_spawn;
+  DevBuf<int32_t> d_order;             // workgroup -> env dispatch order (cost-sorted)
+  DevBuf<uint32_t> d_cost;             // per-env cost of the last env-step (clocks / 64)
   // chunked env-step (gm_step_chunked_kernel): queue counters, per-XCD continuation rings,
   // per-env carry; chunk = substeps per chunk (0: the one-shot kernel)
-  uint32_t* d_chunk_ctr = nullptr;
-  uint64_t* d_chunk_ring = nullptr;
-  GmChunkCarry* d_chunk_carry = nullptr;
-  unsigned long long* d_chunk_st = nullptr;
+  DevBuf<uint32_t> d_chunk_ctr;
+  DevBuf<uint64_t> d_chunk_ring;
+  DevBuf<GmChunkCarry> d_chunk_carry;
+  DevBuf<unsigned long long> d_chunk_st;
   int chunk = 0, chunk_grid = 0, chunk_cap = 0, chunk_margin = 50, chunk_yields = 20, chunk_cmargin = 50;
   int chunk_steal = 1;                 // idle waves resume yielded envs of other XCDs (GM_CHUNK_STEAL=0: off)
   int chunk_prio = 1;                  // issue priority by predicted work left (GM_CHUNK_PRIO=0: off)
   // DUO workgroups (gm_step_kernel<CL, false, true>): two waves per env, the second running
   // the collider concurrently -- for batches small enough that wave slots are spare
   bool duo = false;
-  gm_spawn_params* d_scene = nullptr;  // gm_set_scene_spawn parameters (NULL: plain spawn_object)
+  DevBuf<gm_spawn_params> d_scene;     // gm_set_scene_spawn parameters (empty: plain spawn_object)
   int scene_tries = 0;
   GmSpawnRand spawn_rand{};            // gm_set_random_spawn (enable = 0: spawn tables)
   std::string err;
@@ -117,6 +149,32 @@ static int stage_upload(gm_ctx* c, void* dst, const void* src, size_t bytes) {
   }
   return GM_OK;
 }
+// a thread-per-env kernel on the context's stream
+template <class K, class... A>
+hipError_t launch_per_env(const gm_ctx* c, K kernel, const A&... args) {
+  const int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, c->stream, args...);
+  return hipGetLastError();
+}
+// the caller's per-env mask on the device (dm; NULL without one: every env)
+hipError_t upload_mask(gm_ctx* c, const uint8_t* mask, const uint8_t*& dm) {
+  dm = mask ? c->d_mask.get() : nullptr;
+  return mask ? hipMemcpyAsync(c->d_mask, mask, (size_t)c->n_envs, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+}
+// a device range to the caller's array (host, or device with on_device), complete on return
+int read_back(gm_ctx* c, void* dst, const void* src, size_t bytes, int on_device = 0) {
+  HIPCHK(c, hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GM_OK;
+}
+// gm_reset_kernel: one 64-lane workgroup per env, the envs of the device mask dm (NULL: all),
+// poses from the device table ds (NULL: the context's spawn rule)
+hipError_t launch_reset(gm_ctx* c, const uint8_t* dm, const gm_spawn* ds) {
+  hipLaunchKernelGGL(gm_reset_kernel, dim3(c->n_envs), dim3(64), 0, c->stream, c->d_state, c->d_model, c->d_cfg,
+                     c->d_topo, c->d_eq, dm, ds, c->d_objs, c->n_objects, c->n_envs, c->d_scene, c->scene_tries,
+                     c->d_obs, c->spawn_rand);
+  return hipGetLastError();
+}
 
 bool nseg_supported(int n) {
   switch (n) {
@@ -130,8 +188,8 @@ bool nseg_supported(int n) {
 // job: a rollout's (rollout_job; it needs the chunked queue), NULL: one plain env-step per env
 hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, const GmRolloutJob* job = nullptr) {
   // the full env-step (mode 0) runs in cost-sorted order and records each env's cost
-  const int32_t* order = (mode == 0 && grid == c->n_envs) ? c->d_order : nullptr;
-  uint32_t* cost = (mode == 0 && grid == c->n_envs) ? c->d_cost : nullptr;
+  const int32_t* order = (mode == 0 && grid == c->n_envs) ? c->d_order.get() : nullptr;
+  uint32_t* cost = (mode == 0 && grid == c->n_envs) ? c->d_cost.get() : nullptr;
   // the chunked work queue (gm_chunkq.h, gm_kernels.hip chunked_env_steps): one workgroup per
   // resident wave slot, each pulling env chunks until every env has finished
   const bool chunked = order && c->chunk > 0 && c->chunk_grid > 0 && dbg.phase == nullptr;
@@ -420,33 +478,33 @@ int gm_create(const gm_model* model, const gm_config* cfg, const gm_object* obje
   HIPCHK(c, hipEventCreate(&c->ev1));
   HIPCHK(c, hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming));
   c->stage_bytes = std::max(sizeof(float) * (size_t)n_envs * GM_ACTION_CODE_COUNT, sizeof(int32_t) * (size_t)n_envs);
-  HIPCHK(c, hipHostMalloc(&c->h_stage, c->stage_bytes, hipHostMallocDefault));
-  HIPCHK(c, hipMalloc(&c->d_state, sizeof(GmEnvState) * (size_t)n_envs));
-  HIPCHK(c, hipMalloc(&c->d_scratch, std::max(sizeof(double) * 3 * (size_t)n_envs + (size_t)n_envs + 16,
-                                              sizeof(float) * 5 * (size_t)n_envs)));
-  HIPCHK(c, hipMalloc(&c->d_model, sizeof(gm_model)));
-  HIPCHK(c, hipMalloc(&c->d_cfg, sizeof(gm_config)));
-  HIPCHK(c, hipMalloc(&c->d_topo, sizeof(GmTopo)));
-  HIPCHK(c, hipMalloc(&c->d_objs, sizeof(gm_object) * (size_t)n_objects));
-  HIPCHK(c, hipMalloc(&c->d_eq, sizeof(double) * GM_MAX_QPOS));
+  HIPCHK(c, c->h_stage.alloc(c->stage_bytes));
+  HIPCHK(c, c->d_state.alloc((size_t)n_envs));
+  HIPCHK(c, c->d_scratch.alloc(std::max(sizeof(double) * 3 * (size_t)n_envs + (size_t)n_envs + 16,
+                                        sizeof(float) * 5 * (size_t)n_envs)));
+  HIPCHK(c, c->d_model.alloc(1));
+  HIPCHK(c, c->d_cfg.alloc(1));
+  HIPCHK(c, c->d_topo.alloc(1));
+  HIPCHK(c, c->d_objs.alloc((size_t)n_objects));
+  HIPCHK(c, c->d_eq.alloc(GM_MAX_QPOS));
   {
     const size_t obs_b = sizeof(float) * (size_t)n_envs * (cfg->n_obs > 0 ? cfg->n_obs : 1);
     const size_t rew_b = sizeof(float) * (size_t)n_envs;
     c->out_bytes = obs_b + rew_b + (size_t)n_envs;
-    HIPCHK(c, hipMalloc(&c->d_out, c->out_bytes));
-    HIPCHK(c, hipHostMalloc(&c->h_out, c->out_bytes, hipHostMallocDefault));
-    c->d_obs = static_cast<float*>(c->d_out);
-    c->d_rew = reinterpret_cast<float*>(static_cast<char*>(c->d_out) + obs_b);
-    c->d_done = reinterpret_cast<uint8_t*>(static_cast<char*>(c->d_out) + obs_b + rew_b);
+    HIPCHK(c, c->d_out.alloc(c->out_bytes));
+    HIPCHK(c, c->h_out.alloc(c->out_bytes));
+    c->d_obs = reinterpret_cast<float*>(c->d_out.get());
+    c->d_rew = reinterpret_cast<float*>(c->d_out + obs_b);
+    c->d_done = reinterpret_cast<uint8_t*>(c->d_out + obs_b + rew_b);
   }
-  HIPCHK(c, hipMalloc(&c->d_act, sizeof(float) * (size_t)n_envs * GM_ACTION_CODE_COUNT));
-  HIPCHK(c, hipMalloc(&c->d_dact, sizeof(int32_t) * (size_t)n_envs));
-  HIPCHK(c, hipMalloc(&c->d_mask, (size_t)n_envs));
-  HIPCHK(c, hipMalloc(&c->d_spawn, sizeof(gm_spawn) * (size_t)n_envs));
-  HIPCHK(c, hipMalloc(&c->d_order, sizeof(int32_t) * (size_t)n_envs));
+  HIPCHK(c, c->d_act.alloc((size_t)n_envs * GM_ACTION_CODE_COUNT));
+  HIPCHK(c, c->d_dact.alloc((size_t)n_envs));
+  HIPCHK(c, c->d_mask.alloc((size_t)n_envs));
+  HIPCHK(c, c->d_spawn.alloc((size_t)n_envs));
+  HIPCHK(c, c->d_order.alloc((size_t)n_envs));
   // two halves: [0, n) the costs the current launch is ordered and scheduled by (read-only
   // during it), [n, 2n) the costs it records; gm_dispatch_order_kernel moves them over
-  HIPCHK(c, hipMalloc(&c->d_cost, sizeof(uint32_t) * 2 * (size_t)n_envs));
+  HIPCHK(c, c->d_cost.alloc(2 * (size_t)n_envs));
   HIPCHK(c, hipMemsetAsync(c->d_cost, 0, sizeof(uint32_t) * 2 * (size_t)n_envs, c->stream));
   {
     // chunked env-step: as many workgroups as wave slots are resident (occupancy query),
@@ -483,14 +541,14 @@ int gm_create(const gm_model* model, const gm_config* cfg, const gm_object* obje
     // envs, so the work queue hands envs off between waves)
     if (const char* e5 = std::getenv("GM_CHUNK_GRID")) c->chunk_grid = std::max(1, std::min(c->chunk_grid, std::atoi(e5)));
     c->chunk_cap = n_envs + c->chunk_grid;
-    HIPCHK(c, hipMalloc(&c->d_chunk_ctr, sizeof(uint32_t) * GM_CQ_ALLOC));
+    HIPCHK(c, c->d_chunk_ctr.alloc(GM_CQ_ALLOC));
     HIPCHK(c, hipMemsetAsync(c->d_chunk_ctr, 0, sizeof(uint32_t) * GM_CQ_ALLOC, c->stream));
     // [0, 16) launch stats, then per workgroup its end of work, then per env its start and finish
     const size_t st_words = 16 + (size_t)c->chunk_grid + 2 * (size_t)n_envs;
-    HIPCHK(c, hipMalloc(&c->d_chunk_st, sizeof(unsigned long long) * st_words));
+    HIPCHK(c, c->d_chunk_st.alloc(st_words));
     HIPCHK(c, hipMemsetAsync(c->d_chunk_st, 0, sizeof(unsigned long long) * st_words, c->stream));
-    HIPCHK(c, hipMalloc(&c->d_chunk_ring, sizeof(uint64_t) * 8 * GM_CQ_NB * (size_t)c->chunk_cap));
-    HIPCHK(c, hipMalloc(&c->d_chunk_carry, sizeof(GmChunkCarry) * (size_t)n_envs));
+    HIPCHK(c, c->d_chunk_ring.alloc(8 * GM_CQ_NB * (size_t)c->chunk_cap));
+    HIPCHK(c, c->d_chunk_carry.alloc((size_t)n_envs));
     HIPCHK(c, hipMemsetAsync(c->d_chunk_ring, 0, sizeof(uint64_t) * 8 * GM_CQ_NB * (size_t)c->chunk_cap, c->stream));
   }
   hipLaunchKernelGGL(gm_dispatch_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_cost, c->d_order, n_envs,
@@ -523,7 +581,7 @@ int gm_create(const gm_model* model, const gm_config* cfg, const gm_object* obje
     hipLaunchKernelGGL(gm_settle_init_kernel, dim3(1), dim3(1), 0, c->stream, c->d_state, c->d_model, c->d_topo, c->d_objs);
     DebugOut dbg{nullptr, nullptr, nullptr, nullptr, nullptr};
     HIPCHK(c, launch_step(c, 1, 1, 1, dbg));
-    HIPCHK(c, hipMemcpyAsync(c->d_eq, reinterpret_cast<char*>(c->d_state) + offsetof(GmEnvHot, qpos), sizeof(double) * GM_MAX_QPOS, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_eq, reinterpret_cast<char*>(c->d_state.get()) + offsetof(GmEnvHot, qpos), sizeof(double) * GM_MAX_QPOS, hipMemcpyDeviceToDevice, c->stream));
     std::lock_guard<std::mutex> lk(g_settle_mu);
     if (g_settle_cache_on && (!g_settle_valid || g_settle_nseg != c->model.n_seg)) {
       HIPCHK(c, hipMemcpyAsync(g_settle_eq, c->d_eq, sizeof(double) * GM_MAX_QPOS, hipMemcpyDeviceToHost, c->stream));
@@ -544,15 +602,8 @@ void gm_destroy(gm_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(c->d_state); (void)hipFree(c->d_model); (void)hipFree(c->d_cfg); (void)hipFree(c->d_topo); (void)hipFree(c->d_objs);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  if (c->h_out) (void)hipHostFree(c->h_out);
+  // the events and the stream after the last synchronise, by hand; the buffers with the struct
   if (c->stage_ev) (void)hipEventDestroy(c->stage_ev);
-  (void)hipFree(c->d_eq); (void)hipFree(c->d_out); (void)hipFree(c->d_act);
-  (void)hipFree(c->d_dact); (void)hipFree(c->d_mask); (void)hipFree(c->d_spawn); (void)hipFree(c->d_scratch);
-  (void)hipFree(c->d_order); (void)hipFree(c->d_cost); (void)hipFree(c->d_scene);
-  (void)hipFree(c->d_chunk_ctr); (void)hipFree(c->d_chunk_ring); (void)hipFree(c->d_chunk_carry);
-  (void)hipFree(c->d_chunk_st);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -576,18 +627,11 @@ int gm_update_config(gm_ctx* c, const gm_config* cfg) {
 int gm_reset(gm_ctx* c, const uint8_t* mask, const gm_spawn* spawn) {
   if (!c) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  const uint8_t* dm = nullptr;
-  const gm_spawn* ds = nullptr;
-  if (mask) { HIPCHK(c, hipMemcpyAsync(c->d_mask, mask, (size_t)c->n_envs, hipMemcpyHostToDevice, c->stream)); dm = c->d_mask; }
-  if (spawn) {
+  const uint8_t* dm;
+  HIPCHK(c, upload_mask(c, mask, dm));
+  if (spawn)
     HIPCHK(c, hipMemcpyAsync(c->d_spawn, spawn, sizeof(gm_spawn) * (size_t)c->n_envs, hipMemcpyHostToDevice, c->stream));
-    ds = c->d_spawn;
-  }
-  // gm_reset_kernel: one 64-lane workgroup per env
-  hipLaunchKernelGGL(gm_reset_kernel, dim3(c->n_envs), dim3(64), 0, c->stream, c->d_state, c->d_model, c->d_cfg,
-                     c->d_topo, c->d_eq, dm, ds, c->d_objs, c->n_objects, c->n_envs, c->d_scene, c->scene_tries,
-                     c->d_obs, c->spawn_rand);
-  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, launch_reset(c, dm, spawn ? c->d_spawn.get() : nullptr));
   if (mask || spawn) HIPCHK(c, hipStreamSynchronize(c->stream));   // host buffers may be reused
   return GM_OK;
 }
@@ -595,13 +639,10 @@ int gm_reset(gm_ctx* c, const uint8_t* mask, const gm_spawn* spawn) {
 int gm_spawn_object(gm_ctx* c, const uint8_t* mask, const gm_spawn* spawn) {
   if (!c || !spawn) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  const uint8_t* dm = nullptr;
-  if (mask) { HIPCHK(c, hipMemcpyAsync(c->d_mask, mask, (size_t)c->n_envs, hipMemcpyHostToDevice, c->stream)); dm = c->d_mask; }
+  const uint8_t* dm;
+  HIPCHK(c, upload_mask(c, mask, dm));
   HIPCHK(c, hipMemcpyAsync(c->d_spawn, spawn, sizeof(gm_spawn) * (size_t)c->n_envs, hipMemcpyHostToDevice, c->stream));
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_spawn_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_topo, dm,
-                     c->d_spawn, c->d_objs, c->n_objects, c->n_envs);
-  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, launch_per_env(c, gm_spawn_kernel, c->d_state, c->d_topo, dm, c->d_spawn, c->d_objs, c->n_objects, c->n_envs));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GM_OK;
 }
@@ -610,34 +651,25 @@ int gm_set_motor_target(gm_ctx* c, const uint8_t* mask, const double* xyz, int n
   if (!c || !xyz || (n_xyz != 1 && n_xyz != c->n_envs)) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)c->n_envs;
-  const uint8_t* dm = nullptr;
-  if (mask) { HIPCHK(c, hipMemcpyAsync(c->d_mask, mask, n, hipMemcpyHostToDevice, c->stream)); dm = c->d_mask; }
-  double* d_xyz = static_cast<double*>(c->d_scratch);
+  const uint8_t* dm;
+  HIPCHK(c, upload_mask(c, mask, dm));
+  double* d_xyz = reinterpret_cast<double*>(c->d_scratch.get());
   uint8_t* d_ok = reinterpret_cast<uint8_t*>(d_xyz + 3 * n);
   HIPCHK(c, hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * (size_t)n_xyz, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(d_ok, 1, n, c->stream));
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_motor_target_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, dm, d_xyz,
-                     n_xyz == c->n_envs ? 1 : 0, d_ok, c->n_envs);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && in_limits) e = hipMemcpyAsync(in_limits, d_ok, n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // xyz / in_limits: host arrays
-  HIPCHK(c, e);
+  HIPCHK(c, launch_per_env(c, gm_motor_target_kernel, c->d_state, dm, d_xyz, n_xyz == c->n_envs ? 1 : 0, d_ok,
+                           c->n_envs));
+  if (in_limits) HIPCHK(c, hipMemcpyAsync(in_limits, d_ok, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // xyz / in_limits: host arrays
   return GM_OK;
 }
 
 int gm_get_sensor_si(gm_ctx* c, float* out) {
   if (!c || !out) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t n = (size_t)c->n_envs;
-  float* d_out = static_cast<float*>(c->d_scratch);
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_sensor_si_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, d_out, c->n_envs);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(float) * 5 * n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  HIPCHK(c, e);
-  return GM_OK;
+  float* d_out = reinterpret_cast<float*>(c->d_scratch.get());
+  HIPCHK(c, launch_per_env(c, gm_sensor_si_kernel, c->d_state, d_out, c->n_envs));
+  return read_back(c, out, d_out, sizeof(float) * 5 * (size_t)c->n_envs);
 }
 
 int gm_set_action(gm_ctx* c, const float* actions, int on_device) {
@@ -649,10 +681,7 @@ int gm_set_action(gm_ctx* c, const float* actions, int on_device) {
     if (rc != GM_OK) return rc;
     da = c->d_act;
   }
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_action_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_model, c->d_cfg,
-                     da, (const int32_t*)nullptr, c->n_envs);
-  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, launch_per_env(c, gm_action_kernel, c->d_state, c->d_model, c->d_cfg, da, nullptr, c->n_envs));
   return GM_OK;
 }
 
@@ -665,10 +694,7 @@ int gm_set_discrete_action(gm_ctx* c, const int32_t* actions, int on_device) {
     if (rc != GM_OK) return rc;
     da = c->d_dact;
   }
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_action_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_model, c->d_cfg,
-                     (const float*)nullptr, da, c->n_envs);
-  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, launch_per_env(c, gm_action_kernel, c->d_state, c->d_model, c->d_cfg, nullptr, da, c->n_envs));
   return GM_OK;
 }
 
@@ -685,82 +711,55 @@ int gm_spawn_into_scene(gm_ctx* c, const uint8_t* mask, const gm_spawn_params* p
     if (!spawn_grid_ok(params[i]))
       return fail(c, GM_E_ARG, "gm_spawn_into_scene: spawn grid empty or larger than GM_SPAWN_MAX_XY / GM_SPAWN_MAX_ROT");
   HIPCHK(c, hipSetDevice(c->device));
-  gm_spawn_params* dp = nullptr;
-  uint8_t* dok = nullptr;
-  HIPCHK(c, hipMalloc(&dp, sizeof(gm_spawn_params) * (size_t)n_params));
-  HIPCHK(c, hipMalloc(&dok, (size_t)c->n_envs));
+  DevBuf<gm_spawn_params> dp;   // (released on return: after the synchronise below, or on an error)
+  DevBuf<uint8_t> dok;
+  HIPCHK(c, dp.alloc((size_t)n_params));
+  HIPCHK(c, dok.alloc((size_t)c->n_envs));
   HIPCHK(c, hipMemcpyAsync(dp, params, sizeof(gm_spawn_params) * (size_t)n_params, hipMemcpyHostToDevice, c->stream));
-  const uint8_t* dm = nullptr;
-  if (mask) { HIPCHK(c, hipMemcpyAsync(c->d_mask, mask, (size_t)c->n_envs, hipMemcpyHostToDevice, c->stream)); dm = c->d_mask; }
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_spawn_into_scene_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_model,
-                     c->d_topo, c->d_objs, c->n_objects, dm, dp, n_params, dok, c->n_envs);
-  HIPCHK(c, hipGetLastError());
+  const uint8_t* dm;
+  HIPCHK(c, upload_mask(c, mask, dm));
+  HIPCHK(c, launch_per_env(c, gm_spawn_into_scene_kernel, c->d_state, c->d_model, c->d_topo, c->d_objs, c->n_objects, dm,
+                           dp, n_params, dok, c->n_envs));
   if (ok) HIPCHK(c, hipMemcpyAsync(ok, dok, (size_t)c->n_envs, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(dp);
-  (void)hipFree(dok);
   return GM_OK;
 }
 
 int gm_set_scene_spawn(gm_ctx* c, const gm_spawn_params* params, int max_tries) {
   if (!c) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  if (!params) { c->scene_tries = 0; HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_scene); c->d_scene = nullptr; return GM_OK; }
+  if (!params) { c->scene_tries = 0; HIPCHK(c, hipStreamSynchronize(c->stream)); c->d_scene.reset(); return GM_OK; }
   if (max_tries < 1 || !spawn_grid_ok(*params)) return fail(c, GM_E_ARG, "gm_set_scene_spawn: max_tries < 1 or bad spawn grid");
-  if (!c->d_scene) HIPCHK(c, hipMalloc(&c->d_scene, sizeof(gm_spawn_params)));
+  if (!c->d_scene) HIPCHK(c, c->d_scene.alloc(1));
   HIPCHK(c, hipMemcpyAsync(c->d_scene, params, sizeof(gm_spawn_params), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->scene_tries = max_tries;
   return GM_OK;
 }
 
+// the driver's action fractions for every env's current state (gm_driver_action_kernel, mode: a
+// GmDriver) into the caller's device array, or through d_act into its host array
+static int driver_actions_out(gm_ctx* c, int mode, uint64_t seed, float jitter, float* out, int on_device) {
+  HIPCHK(c, hipSetDevice(c->device));
+  float* d = on_device ? out : c->d_act.get();
+  HIPCHK(c, launch_per_env(c, gm_driver_action_kernel, c->d_state, c->d_model, c->d_cfg, d, c->n_envs, seed,
+                           (long long)c->env_offset, jitter, mode));
+  return on_device ? (int)GM_OK : read_back(c, out, d, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions);
+}
+
 int gm_scripted_actions(gm_ctx* c, uint64_t seed, float jitter, float* out, int on_device) {
   if (!c || !out) return GM_E_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  float* d = on_device ? out : c->d_act;
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_scripted_action_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_cfg, d,
-                     c->n_envs, seed, (long long)c->env_offset, jitter);
-  HIPCHK(c, hipGetLastError());
-  if (!on_device) {
-    HIPCHK(c, hipMemcpyAsync(out, d, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return GM_OK;
+  return driver_actions_out(c, GM_DRV_SCRIPT, seed, jitter, out, on_device);
 }
 
 int gm_program_actions(gm_ctx* c, uint64_t seed, float jitter, int mode, float* out, int on_device) {
-  if (!c || !out || (mode != 3 && mode != 4)) return GM_E_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  float* d = on_device ? out : c->d_act;
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_program_action_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_model,
-                     c->d_cfg, d, c->n_envs, seed, (long long)c->env_offset, jitter, mode);
-  HIPCHK(c, hipGetLastError());
-  if (!on_device) {
-    HIPCHK(c, hipMemcpyAsync(out, d, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return GM_OK;
+  if (!c || !out || (mode != GM_DRV_PROGRAM && mode != GM_DRV_MIX)) return GM_E_ARG;
+  return driver_actions_out(c, mode, seed, jitter, out, on_device);
 }
 
 int gm_random_actions(gm_ctx* c, uint64_t seed, float* out, int on_device) {
   if (!c || !out) return GM_E_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  float* d = on_device ? out : c->d_act;
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_random_action_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_cfg, d,
-                     c->n_envs, seed, (long long)c->env_offset);
-  HIPCHK(c, hipGetLastError());
-  if (!on_device) {
-    HIPCHK(c, hipMemcpyAsync(out, d, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return GM_OK;
+  return driver_actions_out(c, GM_DRV_RANDOM, seed, 0.0f, out, on_device);
 }
 
 int gm_rollout(gm_ctx* c, int n_steps, const gm_rollout_params* p, gm_episode_end* records) {
@@ -777,9 +776,7 @@ int gm_rollout(gm_ctx* c, int n_steps, const gm_rollout_params* p, gm_episode_en
   return per_step_rollout(
       c, n_steps, p->max_episode_steps, records,
       [&](int) {
-        const int rc = p->action_mode == GM_DRV_SCRIPT   ? gm_scripted_actions(c, p->seed, p->jitter, c->d_act, 1)
-                       : p->action_mode == GM_DRV_RANDOM ? gm_random_actions(c, p->seed, c->d_act, 1)
-                                                         : gm_program_actions(c, p->seed, p->jitter, p->action_mode, c->d_act, 1);
+        const int rc = driver_actions_out(c, p->action_mode, p->seed, p->jitter, c->d_act, 1);
         return rc == GM_OK ? gm_set_action(c, c->d_act, 1) : rc;
       },
       [](int) { return (int)GM_OK; });
@@ -814,17 +811,18 @@ float yield_point_load(const gm_model& m) {
   return F_max;
 }
 
-struct CalCtx {
+// (a base class: destroyed after CalCtx's members, so the four buffers go before their context)
+struct CalOwnCtx {
   gm_ctx* c = nullptr;
+  ~CalOwnCtx() { gm_destroy(c); }
+};
+struct CalCtx : CalOwnCtx {
   int nb = 0;
-  double* d_dt = nullptr;
-  int32_t* d_steps = nullptr;
-  uint8_t* d_bad = nullptr;
-  float* d_gauge = nullptr;
+  DevBuf<double> d_dt;
+  DevBuf<int32_t> d_steps;
+  DevBuf<uint8_t> d_bad;
+  DevBuf<float> d_gauge;
   std::vector<gm_spawn> spawn;
-  ~CalCtx() {
-    if (c) { (void)hipFree(d_dt); (void)hipFree(d_steps); (void)hipFree(d_bad); (void)hipFree(d_gauge); gm_destroy(c); }
-  }
   // reset the first n envs (object 0 at the origin, as MjClass::reset leaves the scene),
   // give env i timestep dt[i], steps[i] substeps and the tip load, run them, read BADQACC
   int run(const std::vector<double>& dt, const std::vector<int32_t>& steps, double tip, std::vector<uint8_t>& bad,
@@ -845,7 +843,7 @@ struct CalCtx {
     bad.assign(n, 0);
     HIPCHK(c, hipMemcpyAsync(bad.data(), d_bad, n, hipMemcpyDeviceToHost, c->stream));
     if (ran0)   // substeps env 0 made (GmEnvState::cal_steps after the run)
-      HIPCHK(c, hipMemcpyAsync(ran0, reinterpret_cast<char*>(c->d_state) + offsetof(GmEnvHot, cal_steps), sizeof(int32_t),
+      HIPCHK(c, hipMemcpyAsync(ran0, reinterpret_cast<char*>(c->d_state.get()) + offsetof(GmEnvHot, cal_steps), sizeof(int32_t),
                                hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return GM_OK;
@@ -864,10 +862,10 @@ int gm_calibrate(const gm_model* model, const gm_config* cfg, const gm_object* o
   int rc = gm_create(model, &cc, objects, n_objects, k.nb, 0, device, 0, &k.c);
   if (rc != GM_OK) return rc;
   gm_ctx* c = k.c;
-  HIPCHK(c, hipMalloc(&k.d_dt, sizeof(double) * k.nb));
-  HIPCHK(c, hipMalloc(&k.d_steps, sizeof(int32_t) * k.nb));
-  HIPCHK(c, hipMalloc(&k.d_bad, k.nb));
-  HIPCHK(c, hipMalloc(&k.d_gauge, sizeof(float)));
+  HIPCHK(c, k.d_dt.alloc(k.nb));
+  HIPCHK(c, k.d_steps.alloc(k.nb));
+  HIPCHK(c, k.d_bad.alloc(k.nb));
+  HIPCHK(c, k.d_gauge.alloc(1));
   k.spawn.assign(k.nb, gm_spawn{0, 0.0, 0.0, 0.0});
 
   double timestep = model->timestep;
@@ -1002,12 +1000,20 @@ int gm_step(gm_ctx* c) {
   return timed_launch(c, nullptr);
 }
 
+// the last launch's queue counters (gm_chunkq.h GmCqCounter) and, with times, its time slots
+static int read_chunk_counters(gm_ctx* c, uint32_t (&w)[GM_CQC_N], uint64_t* times = nullptr) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (times)
+    HIPCHK(c, hipMemcpyAsync(times, c->d_chunk_st + GM_CQT_LAST, sizeof(uint64_t) * GM_CQT_N, hipMemcpyDeviceToHost,
+                             c->stream));
+  return read_back(c, w, c->d_chunk_ctr + GM_CQ_LAST, sizeof(w));
+}
+
 int gm_chunk_claim_waits(gm_ctx* c, uint32_t* out2) {
   if (!c || !out2) return GM_E_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  uint32_t w[GM_CQC_N];   // the last launch's counters (gm_chunkq.h GmCqCounter)
-  HIPCHK(c, hipMemcpyAsync(w, c->d_chunk_ctr + GM_CQ_LAST, sizeof(w), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint32_t w[GM_CQC_N];
+  const int rc = read_chunk_counters(c, w);
+  if (rc != GM_OK) return rc;
   out2[0] = w[GM_CQC_CLAIM_WAITS]; out2[1] = w[GM_CQC_CLAIM_POLLS];
   return GM_OK;
 }
@@ -1017,8 +1023,8 @@ int gm_chunk_job_stats(gm_ctx* c, uint32_t* clk, int32_t* yields) {
   if (!c->d_chunk_carry) return GM_E_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<GmChunkCarry> h((size_t)c->n_envs);
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->d_chunk_carry, sizeof(GmChunkCarry) * h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int rc = read_back(c, h.data(), c->d_chunk_carry, sizeof(GmChunkCarry) * h.size());
+  if (rc != GM_OK) return rc;
   for (int e = 0; e < c->n_envs; e++) {
     if (clk) clk[e] = h[(size_t)e].clk;
     if (yields) yields[e] = h[(size_t)e].job_yields;
@@ -1028,13 +1034,9 @@ int gm_chunk_job_stats(gm_ctx* c, uint32_t* clk, int32_t* yields) {
 
 int gm_chunk_stats(gm_ctx* c, uint32_t* out, uint64_t* times) {
   if (!c || !out) return GM_E_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
   uint32_t w[GM_CQC_N];
-  HIPCHK(c, hipMemcpyAsync(w, c->d_chunk_ctr + GM_CQ_LAST, sizeof(w), hipMemcpyDeviceToHost, c->stream));
-  if (times)
-    HIPCHK(c, hipMemcpyAsync(times, c->d_chunk_st + GM_CQT_LAST, sizeof(uint64_t) * GM_CQT_N, hipMemcpyDeviceToHost,
-                             c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int rc = read_chunk_counters(c, w, times);
+  if (rc != GM_OK) return rc;
   out[0] = std::min<uint32_t>(w[GM_CQC_FRESH], (uint32_t)c->n_envs);
   out[1] = w[GM_CQC_DONE]; out[2] = w[GM_CQC_YIELDS]; out[3] = w[GM_CQC_RESUMES];
   out[4] = (uint32_t)c->chunk; out[5] = (uint32_t)c->chunk_grid;
@@ -1046,10 +1048,8 @@ int gm_chunk_timeline(gm_ctx* c, uint64_t* out, int max_out) {
   if (!c || !out || max_out < 0) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   const int n = std::min(max_out, c->chunk_grid + 2 * c->n_envs);
-  HIPCHK(c, hipMemcpyAsync(out, c->d_chunk_st + GM_CQT_TIMELINE, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost,
-                           c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return n;
+  const int rc = read_back(c, out, c->d_chunk_st + GM_CQT_TIMELINE, sizeof(uint64_t) * (size_t)n);
+  return rc == GM_OK ? n : rc;
 }
 
 int gm_dispatch_info(const gm_ctx* c, int32_t* out) {
@@ -1068,10 +1068,7 @@ int gm_last_step_ms(gm_ctx* c, float* ms) {
 int gm_get_obs(gm_ctx* c, float* out, int on_device) {
   if (!c || !out) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  size_t bytes = sizeof(float) * (size_t)c->n_envs * c->cfg.n_obs;
-  HIPCHK(c, hipMemcpyAsync(out, c->d_obs, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GM_OK;
+  return read_back(c, out, c->d_obs, sizeof(float) * (size_t)c->n_envs * c->cfg.n_obs, on_device);
 }
 
 int gm_get_outputs(gm_ctx* c, float* obs, float* reward, uint8_t* done) {
@@ -1079,12 +1076,12 @@ int gm_get_outputs(gm_ctx* c, float* obs, float* reward, uint8_t* done) {
   HIPCHK(c, hipSetDevice(c->device));
   // one copy of the contiguous obs / reward / done block into pinned memory (one DMA, no
   // pageable staging), then the three host copies
-  HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, c->out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const char* h = static_cast<const char*>(c->h_out);
+  const int rc = read_back(c, c->h_out, c->d_out, c->out_bytes);
+  if (rc != GM_OK) return rc;
+  const char* h = c->h_out;
   const size_t obs_b = sizeof(float) * (size_t)c->n_envs * c->cfg.n_obs;
-  const size_t off_rew = reinterpret_cast<const char*>(c->d_rew) - static_cast<const char*>(c->d_out);
-  const size_t off_done = reinterpret_cast<const char*>(c->d_done) - static_cast<const char*>(c->d_out);
+  const size_t off_rew = reinterpret_cast<const char*>(c->d_rew) - c->d_out.get();
+  const size_t off_done = reinterpret_cast<const char*>(c->d_done) - c->d_out.get();
   std::memcpy(obs, h, obs_b);
   std::memcpy(reward, h + off_rew, sizeof(float) * (size_t)c->n_envs);
   std::memcpy(done, h + off_done, (size_t)c->n_envs);
@@ -1101,12 +1098,14 @@ int gm_get_reward_done(gm_ctx* c, float* reward, uint8_t* done, int on_device) {
   return GM_OK;
 }
 
+// every env's state record into the host array out
+static int fetch_states_to(gm_ctx* c, void* out) {
+  HIPCHK(c, hipSetDevice(c->device));
+  return read_back(c, out, c->d_state, sizeof(GmEnvState) * (size_t)c->n_envs);
+}
 static int fetch_states(gm_ctx* c, std::vector<GmEnvState>& h) {
   h.resize(c->n_envs);
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->d_state, sizeof(GmEnvState) * (size_t)c->n_envs, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GM_OK;
+  return fetch_states_to(c, h.data());
 }
 
 int gm_get_event_rows(gm_ctx* c, int32_t* rows, int32_t* absc, float* lastv) {
@@ -1161,10 +1160,7 @@ int64_t gm_env_state_size(void) { return (int64_t)sizeof(GmEnvState); }
 
 int gm_get_env_states(gm_ctx* c, void* out) {
   if (!c || !out) return GM_E_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(out, c->d_state, sizeof(GmEnvState) * (size_t)c->n_envs, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GM_OK;
+  return fetch_states_to(c, out);
 }
 
 int gm_set_env_states(gm_ctx* c, const void* in) {
@@ -1213,21 +1209,22 @@ int gm_get_overflow(gm_ctx* c, int32_t* counts) {
 void* gm_device_obs(gm_ctx* c) { return c ? c->d_obs : nullptr; }
 void* gm_device_reward(gm_ctx* c) { return c ? c->d_rew : nullptr; }
 void* gm_device_done(gm_ctx* c) { return c ? c->d_done : nullptr; }
-void* gm_device_actions(gm_ctx* c) { return c ? c->d_act : nullptr; }
+void* gm_device_actions(gm_ctx* c) { return c ? c->d_act.get() : nullptr; }
 void* gm_stream(gm_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 int gm_debug_substep(gm_ctx* c, int32_t* ncon, double* contact, double* efc_force, double* qacc, int32_t* nefc,
                      double* obj_wrench) {
   if (!c) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  int32_t *d_ncon, *d_nefc; double *d_con, *d_f, *d_q, *d_w;
+  DevBuf<int32_t> d_ncon, d_nefc;   // (released on return: after the synchronise below, or on an error)
+  DevBuf<double> d_con, d_f, d_q, d_w;
   size_t n = (size_t)c->n_envs;
-  HIPCHK(c, hipMalloc(&d_ncon, sizeof(int32_t) * n));
-  HIPCHK(c, hipMalloc(&d_nefc, sizeof(int32_t) * n));
-  HIPCHK(c, hipMalloc(&d_con, sizeof(double) * n * GM_MAX_CON * 16));
-  HIPCHK(c, hipMalloc(&d_f, sizeof(double) * n * GM_MAX_EFC));
-  HIPCHK(c, hipMalloc(&d_q, sizeof(double) * n * GM_MAX_DOF));
-  HIPCHK(c, hipMalloc(&d_w, sizeof(double) * n * 6));
+  HIPCHK(c, d_ncon.alloc(n));
+  HIPCHK(c, d_nefc.alloc(n));
+  HIPCHK(c, d_con.alloc(n * GM_MAX_CON * 16));
+  HIPCHK(c, d_f.alloc(n * GM_MAX_EFC));
+  HIPCHK(c, d_q.alloc(n * GM_MAX_DOF));
+  HIPCHK(c, d_w.alloc(n * 6));
   DebugOut dbg{d_ncon, d_con, d_f, d_q, nullptr, d_nefc, d_w};
   HIPCHK(c, launch_step(c, c->n_envs, c->n_envs, 2, dbg));
   if (ncon) HIPCHK(c, hipMemcpyAsync(ncon, d_ncon, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
@@ -1237,8 +1234,6 @@ int gm_debug_substep(gm_ctx* c, int32_t* ncon, double* contact, double* efc_forc
   if (qacc) HIPCHK(c, hipMemcpyAsync(qacc, d_q, sizeof(double) * n * GM_MAX_DOF, hipMemcpyDeviceToHost, c->stream));
   if (obj_wrench) HIPCHK(c, hipMemcpyAsync(obj_wrench, d_w, sizeof(double) * n * 6, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d_ncon); (void)hipFree(d_nefc); (void)hipFree(d_con); (void)hipFree(d_f); (void)hipFree(d_q);
-  (void)hipFree(d_w);
   return GM_OK;
 }
 
@@ -1259,40 +1254,29 @@ int gm_autoreset_episodes(gm_ctx* c, int max_episode_steps, const gm_spawn* spaw
   static_assert(sizeof(gm_episode_end) == 12, "episode-end record is 3 x 4 bytes");
   if (!c) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  const gm_spawn* ds = nullptr;
+  const gm_spawn* ds = spawn;
   if (spawn && !spawn_on_device) {
     HIPCHK(c, hipMemcpyAsync(c->d_spawn, spawn, sizeof(gm_spawn) * (size_t)c->n_envs, hipMemcpyHostToDevice, c->stream));
     ds = c->d_spawn;
-  } else if (spawn) {
-    ds = spawn;
   }
-  int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_autoreset_mask_kernel, dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_done,
-                     max_episode_steps, c->d_mask, returns, episodes, c->n_envs);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(gm_reset_kernel, dim3(c->n_envs), dim3(64), 0, c->stream, c->d_state, c->d_model, c->d_cfg,
-                     c->d_topo, c->d_eq, c->d_mask, ds, c->d_objs, c->n_objects, c->n_envs, c->d_scene,
-                     c->scene_tries, c->d_obs, c->spawn_rand);
-  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, launch_per_env(c, gm_autoreset_mask_kernel, c->d_state, c->d_done, max_episode_steps, c->d_mask, returns,
+                           episodes, c->n_envs));
+  HIPCHK(c, launch_reset(c, c->d_mask, ds));
   if (spawn && !spawn_on_device) HIPCHK(c, hipStreamSynchronize(c->stream));
   return GM_OK;
 }
 
-void* gm_device_reset_mask(gm_ctx* c) { return c ? (void*)c->d_mask : nullptr; }
+void* gm_device_reset_mask(gm_ctx* c) { return c ? c->d_mask.get() : nullptr; }
 
 int gm_step_profiled(gm_ctx* c, uint64_t* phase_cycles) {
   if (!c || !phase_cycles) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  size_t n = (size_t)c->n_envs;
-  unsigned long long* d_ph;
-  HIPCHK(c, hipMalloc(&d_ph, sizeof(unsigned long long) * n * GM_NPHASE));
+  const size_t n = (size_t)c->n_envs * GM_NPHASE;
+  DevBuf<unsigned long long> d_ph;   // (released on return: after read_back's synchronise, or on an error)
+  HIPCHK(c, d_ph.alloc(n));
   DebugOut dbg{nullptr, nullptr, nullptr, nullptr, d_ph};
   HIPCHK(c, launch_step(c, c->n_envs, c->n_envs, 0, dbg));
-  HIPCHK(c, hipMemcpyAsync(phase_cycles, d_ph, sizeof(unsigned long long) * n * GM_NPHASE, hipMemcpyDeviceToHost,
-                           c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d_ph);
-  return GM_OK;
+  return read_back(c, phase_cycles, d_ph, sizeof(unsigned long long) * n);
 }
 
 }  // extern "C"
@@ -1301,10 +1285,10 @@ int gm_step_profiled(gm_ctx* c, uint64_t* phase_cycles) {
 struct gm_policy {
   gm_ctx* ctx = nullptr;
   GpNet net{};
-  float* d_params = nullptr;
-  int32_t* d_actions = nullptr;
-  float* d_q = nullptr;
-  float* d_eps = nullptr;      // gm_policy_rollout's exploration thresholds, one per env-step
+  DevBuf<float> d_params;
+  DevBuf<int32_t> d_actions;
+  DevBuf<float> d_q;
+  DevBuf<float> d_eps;         // gm_policy_rollout's exploration thresholds, one per env-step
   int eps_cap = 0;
 };
 
@@ -1370,9 +1354,9 @@ int gm_policy_create(gm_ctx* c, const int32_t* sizes, int n_sizes, const float* 
   gm_policy* p = new gm_policy;
   p->ctx = c;
   p->net = P;
-  hipError_t e = hipMalloc(&p->d_params, sizeof(float) * (size_t)total);
-  if (e == hipSuccess) e = hipMalloc(&p->d_actions, sizeof(int32_t) * (size_t)c->n_envs);
-  if (e == hipSuccess) e = hipMalloc(&p->d_q, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions);
+  hipError_t e = p->d_params.alloc((size_t)total);
+  if (e == hipSuccess) e = p->d_actions.alloc((size_t)c->n_envs);
+  if (e == hipSuccess) e = p->d_q.alloc((size_t)c->n_envs * c->cfg.n_actions);
   if (e == hipSuccess)
     e = hipMemcpyAsync(p->d_params, packed.data(), sizeof(float) * (size_t)total, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1390,10 +1374,6 @@ void gm_policy_destroy(gm_policy* p) {
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);   // the stream may still read d_params / d_eps
   }
-  (void)hipFree(p->d_params);
-  (void)hipFree(p->d_actions);
-  (void)hipFree(p->d_q);
-  (void)hipFree(p->d_eps);
   delete p;
 }
 
@@ -1417,10 +1397,8 @@ int gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed
     if (n_steps > p->eps_cap) {
       // (the stream may still read the old buffer: wait before freeing it)
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      (void)hipFree(p->d_eps);
-      p->d_eps = nullptr;
       p->eps_cap = 0;
-      HIPCHK(c, hipMalloc(&p->d_eps, sizeof(float) * (size_t)n_steps));
+      HIPCHK(c, p->d_eps.alloc((size_t)n_steps));
       p->eps_cap = n_steps;
     }
     // eps is the caller's (pageable) array: the copy owns its bytes before the call returns
@@ -1461,8 +1439,8 @@ struct gm_ac {
   int64_t total = 0;           // packed floats
   int64_t n_raw = 0;           // floats of the caller's (state_dict order) parameters
   std::vector<int32_t> asz, csz;
-  float* d_params = nullptr;
-  GaArgs* d_args = nullptr;    // gm_ac_rollout's launch arguments
+  DevBuf<float> d_params;
+  DevBuf<GaArgs> d_args;       // gm_ac_rollout's launch arguments
 };
 
 static_assert(GA_MAX_ACT >= GM_ACTION_CODE_COUNT, "the sampler's rows hold every action");
@@ -1500,8 +1478,16 @@ static void ac_fill(GaArgs& A, const gm_ac* p, const gm_ac_traj* t, int sample, 
 static bool ac_traj_ok(const gm_ac_traj* t) {
   return t && t->capacity >= 1 && t->obs && t->act && t->logp && t->val && t->rew && t->end && t->boot && t->last_val;
 }
-static int ac_launch(gm_ac* p, int what, const GaArgs& A, int k, int max_ep) {
+// One per-step call (what: 0 gm_ac_act, 1 gm_ac_record, 2 gm_ac_finish) on trajectory row k: the
+// checks (bad: the message for a bad buffer, row or noise), the device, gm_ac_kernel
+static int ac_step(gm_ac* p, const gm_ac_traj* t, int k, int what, int max_ep, const char* bad, int sample = 0,
+                   float noise = 0.0f, uint64_t seed = 0, uint64_t decision0 = 0) {
+  if (!p || !p->ctx) return GM_E_ARG;
   gm_ctx* c = p->ctx;
+  if (!ac_traj_ok(t) || k < 0 || k >= t->capacity || !(noise >= 0.0f)) return fail(c, GM_E_ARG, bad);
+  HIPCHK(c, hipSetDevice(c->device));
+  GaArgs A{};
+  ac_fill(A, p, t, sample, noise, seed, decision0);
   const int blocks = (c->n_envs + GP_TILE - 1) / GP_TILE;
   hipLaunchKernelGGL(gm_ac_kernel, dim3(blocks), dim3(64), 0, c->stream, what, c->d_obs, c->d_state, c->d_rew,
                      c->d_done, c->n_envs, (long long)c->env_offset, A, k, max_ep);
@@ -1551,8 +1537,8 @@ int gm_ac_create(gm_ctx* c, const int32_t* actor_sizes, int n_actor, const int32
   p->n_raw = n_raw;
   p->asz.assign(actor_sizes, actor_sizes + n_actor);
   p->csz.assign(critic_sizes, critic_sizes + n_critic);
-  hipError_t e = hipMalloc(&p->d_params, sizeof(float) * (size_t)total);
-  if (e == hipSuccess) e = hipMalloc(&p->d_args, sizeof(GaArgs));
+  hipError_t e = p->d_params.alloc((size_t)total);
+  if (e == hipSuccess) e = p->d_args.alloc(1);
   if (e != hipSuccess) {
     gm_ac_destroy(p);
     return fail(c, GM_E_HIP, std::string("gm_ac_create: ") + hipGetErrorString(e));
@@ -1569,8 +1555,6 @@ void gm_ac_destroy(gm_ac* p) {
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
   }
-  (void)hipFree(p->d_params);
-  (void)hipFree(p->d_args);
   delete p;
 }
 
@@ -1584,39 +1568,21 @@ int gm_ac_set_params(gm_ac* p, const float* params) {
 }
 
 int gm_ac_act(gm_ac* p, const gm_ac_traj* traj, int k, int sample, float noise, uint64_t seed, uint64_t decision) {
-  if (!p || !p->ctx) return GM_E_ARG;
-  gm_ctx* c = p->ctx;
-  if (!ac_traj_ok(traj) || k < 0 || k >= traj->capacity || !(noise >= 0.0f))
-    return fail(c, GM_E_ARG, "gm_ac_act: incomplete trajectory buffer, k outside its capacity or negative noise");
-  HIPCHK(c, hipSetDevice(c->device));
-  GaArgs A{};
   // (the kernel draws with decision0 + k)
-  ac_fill(A, p, traj, sample, noise, seed, decision - (uint64_t)k);
-  const int rc = ac_launch(p, 0, A, k, 0);
+  const int rc =
+      ac_step(p, traj, k, 0, 0, "gm_ac_act: incomplete trajectory buffer, k outside its capacity or negative noise",
+              sample, noise, seed, decision - (uint64_t)k);
   if (rc != GM_OK) return rc;
+  gm_ctx* c = p->ctx;
   return gm_set_action(c, traj->act + (size_t)k * c->n_envs * c->cfg.n_actions, 1);
 }
 
 int gm_ac_record(gm_ac* p, const gm_ac_traj* traj, int k, int max_episode_steps) {
-  if (!p || !p->ctx) return GM_E_ARG;
-  gm_ctx* c = p->ctx;
-  if (!ac_traj_ok(traj) || k < 0 || k >= traj->capacity)
-    return fail(c, GM_E_ARG, "gm_ac_record: incomplete trajectory buffer or k outside its capacity");
-  HIPCHK(c, hipSetDevice(c->device));
-  GaArgs A{};
-  ac_fill(A, p, traj, 0, 0.0f, 0, 0);
-  return ac_launch(p, 1, A, k, max_episode_steps);
+  return ac_step(p, traj, k, 1, max_episode_steps, "gm_ac_record: incomplete trajectory buffer or k outside its capacity");
 }
 
 int gm_ac_finish(gm_ac* p, const gm_ac_traj* traj, int k_last) {
-  if (!p || !p->ctx) return GM_E_ARG;
-  gm_ctx* c = p->ctx;
-  if (!ac_traj_ok(traj) || k_last < 0 || k_last >= traj->capacity)
-    return fail(c, GM_E_ARG, "gm_ac_finish: incomplete trajectory buffer or k_last outside its capacity");
-  HIPCHK(c, hipSetDevice(c->device));
-  GaArgs A{};
-  ac_fill(A, p, traj, 0, 0.0f, 0, 0);
-  return ac_launch(p, 2, A, k_last, 0);
+  return ac_step(p, traj, k_last, 2, 0, "gm_ac_finish: incomplete trajectory buffer or k_last outside its capacity");
 }
 
 int gm_ac_rollout(gm_ac* p, const gm_ac_traj* traj, int n_steps, int sample, float noise, uint64_t seed,
@@ -1648,10 +1614,8 @@ int gm_ac_gae(gm_ctx* c, const gm_ac_traj* traj, int n_steps, float gamma, float
       n_steps < 1 || n_steps > traj->capacity)
     return fail(c, GM_E_ARG, "gm_ac_gae: incomplete trajectory buffer or n_steps outside its capacity");
   HIPCHK(c, hipSetDevice(c->device));
-  const int threads = 64, blocks = (c->n_envs + threads - 1) / threads;
-  hipLaunchKernelGGL(gm_ac_gae_kernel, dim3(blocks), dim3(threads), 0, c->stream, traj->rew, traj->val, traj->end,
-                     traj->boot, traj->last_val, c->n_envs, n_steps, gamma, lam, adv, ret);
-  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, launch_per_env(c, gm_ac_gae_kernel, traj->rew, traj->val, traj->end, traj->boot, traj->last_val, c->n_envs,
+                           n_steps, gamma, lam, adv, ret));
   return GM_OK;
 }
 

@@ -3143,53 +3143,27 @@ extern "C" __global__ void gm_action_kernel(GmEnvState* __restrict__ states, con
 // the palm, lift the base -- indexed by the env's own episode step (num_action_steps),
 // plus uniform jitter per (step, action).  Continuous action fractions in [-1, 1] for
 // the in-use actions (MjClass::set_continous_action order).
-#ifndef GM_CAL_TU   // env-step translation unit only
-extern "C" __global__ void gm_scripted_action_kernel(const GmEnvState* __restrict__ states, const gm_config* __restrict__ C,
-                                                     float* __restrict__ out, int n_envs, uint64_t seed,
-                                                     long long env_offset, float jitter) {
-  const int env = blockIdx.x * blockDim.x + threadIdx.x;
-  if (env >= n_envs) return;
-  const GmEnvState& s = states[env];
-  const int na = C->n_actions;
-  for (int i = 0; i < na; i++) {
-    const int code = C->action_options[i];
-    const int kind = (code >= 0 && code < GM_ACTION_TERMINATION) ? code / 3 : -1;
-    out[(size_t)env * na + i] = gm_script_fraction(seed, env_offset + env, s.episode, s.num_action_steps, i, kind, jitter);
-  }
+// action code -> action kind (gm_settings.def order, three codes a kind); -1: the termination action
+__device__ __forceinline__ int action_kind(int code) {
+  return (code >= 0 && code < GM_ACTION_TERMINATION) ? code / 3 : -1;
 }
-#endif
-
-// the driver's actions for the current state of every env (gm_program_actions): modes 3
-// (grasp program) and 4 (program / scripted mix), thread per env
+// the driver's actions for the current state of every env (gm_scripted_actions, gm_random_actions,
+// gm_program_actions), thread per env: the first loop of driver_actions written to memory, in
+// mode GM_DRV_SCRIPT, _RANDOM (U[-1, 1) per (env, episode, episode step, action) from the
+// counter-based hash, gm_state.h), _PROGRAM or _MIX
 #ifndef GM_CAL_TU   // env-step translation unit only
-extern "C" __global__ void gm_program_action_kernel(const GmEnvState* __restrict__ states, const gm_model* __restrict__ m,
-                                                    const gm_config* __restrict__ C, float* __restrict__ out, int n_envs,
-                                                    uint64_t seed, long long env_offset, float jitter, int mode) {
+extern "C" __global__ void gm_driver_action_kernel(const GmEnvState* __restrict__ states, const gm_model* __restrict__ m,
+                                                   const gm_config* __restrict__ C, float* __restrict__ out, int n_envs,
+                                                   uint64_t seed, long long env_offset, float jitter, int mode) {
   const int env = blockIdx.x * blockDim.x + threadIdx.x;
   if (env >= n_envs) return;
   const GmEnvState& s = states[env];
   const int na = C->n_actions;
   for (int i = 0; i < na; i++) {
-    const int code = C->action_options[i];
-    const int kind = (code >= 0 && code < GM_ACTION_TERMINATION) ? code / 3 : -1;
-    const float v = driver_fraction(s, const_cast<RingRef>(s.ring), m, C, mode, seed, jitter, env_offset + env, i, kind);
+    const float v = driver_fraction(s, const_cast<RingRef>(s.ring), m, C, mode, seed, jitter, env_offset + env, i,
+                                    action_kind(C->action_options[i]));
     out[(size_t)env * na + i] = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
   }
-}
-#endif
-
-// uniform random action fractions (gm_random_actions; the rollout's random mode): U[-1, 1)
-// per (env, episode, episode step, action) from the counter-based hash (gm_state.h)
-#ifndef GM_CAL_TU   // env-step translation unit only
-extern "C" __global__ void gm_random_action_kernel(const GmEnvState* __restrict__ states, const gm_config* __restrict__ C,
-                                                   float* __restrict__ out, int n_envs, uint64_t seed,
-                                                   long long env_offset) {
-  const int env = blockIdx.x * blockDim.x + threadIdx.x;
-  if (env >= n_envs) return;
-  const GmEnvState& s = states[env];
-  const int na = C->n_actions;
-  for (int i = 0; i < na; i++)
-    out[(size_t)env * na + i] = gm_random_fraction(seed, env_offset + env, s.episode, s.num_action_steps, i);
 }
 #endif
 

@@ -134,6 +134,57 @@ def test_random_actions_match_host_mirror(gm):
 
 
 @pytest.mark.gpu
+def test_driver_action_entry_points_agree(gm):
+    """gm_scripted_actions, gm_random_actions and gm_program_actions (modes 3 and 4) on 8 envs
+    of N = 5 fingers, two env-steps into their episodes: the host array (on_device = 0) equals
+    what on_device = 1 writes to gm_device_actions, every fraction lies in [-1, 1], each env's
+    mix row is its program row or its scripted row, and other modes are still refused."""
+    if not gpu_available():
+        pytest.skip("no GPU")
+    import ctypes as C
+    import torch
+    n, seed = 8, 41
+    lib = gm.load_library()
+    p = gm.ModelParams()
+    lib.gm_default_model_params(C.byref(p))
+    p.n_seg, p.timestep = 5, 6.76e-3
+    env = gm.BatchedGripperEnv(n, object_set="set6_synthetic", settings=gm.canonical_settings(noise=True, seed=seed),
+                               seed=seed, model_params=p)
+    try:
+        env.set_scene_spawn(gm.default_spawn_params(), max_tries=3)
+        env.reset()
+        for _ in range(2):
+            env.step(env.scripted_actions(seed))
+        assert (gm.env_state_view(env.env_states())["num_action_steps"] > 0).all()
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        d_act = env.lib.gm_device_actions(env.ctx)
+
+        def both(call):
+            """call(out, on_device) -> rc, through the host array and through d_act"""
+            host = np.zeros((n, env.n_actions), dtype=np.float32)
+            assert call(host.ctypes.data, 0) == 0
+            dev = np.full((n, env.n_actions), np.nan, dtype=np.float32)
+            assert hip.hipMemcpy(d_act, dev.ctypes.data, dev.nbytes, 1) == 0   # (the sentinel, host to device)
+            assert call(d_act, 1) == 0
+            torch.cuda.synchronize()
+            assert hip.hipMemcpy(dev.ctypes.data, d_act, dev.nbytes, 2) == 0   # (device to host)
+            np.testing.assert_array_equal(host, dev)
+            assert host.min() >= -1.0 and host.max() <= 1.0
+            return host
+
+        script = both(lambda out, dev: env.lib.gm_scripted_actions(env.ctx, seed, 0.2, out, dev))
+        both(lambda out, dev: env.lib.gm_random_actions(env.ctx, seed, out, dev))
+        prog = both(lambda out, dev: env.lib.gm_program_actions(env.ctx, seed, 0.2, 3, out, dev))
+        mix = both(lambda out, dev: env.lib.gm_program_actions(env.ctx, seed, 0.2, 4, out, dev))
+        for e in range(n):
+            assert np.array_equal(mix[e], prog[e]) or np.array_equal(mix[e], script[e]), e
+        assert env.lib.gm_program_actions(env.ctx, seed, 0.2, 0, d_act, 1) == -1   # GM_E_ARG
+    finally:
+        env.close()
+
+
+@pytest.mark.gpu
 def test_rollout_equals_per_step_api_full_size(gm):
     """The identity at the headline batch (4096 envs on every XCD's queue, yields and
     cross-XCD resumptions under the default dispatch), 3-step episodes so every env resets
