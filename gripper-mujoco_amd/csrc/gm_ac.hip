@@ -1,7 +1,7 @@
 // gm_ac.hip -- the batched PPO actor-critic kernels (gm_ac_act / gm_ac_record / gm_ac_finish)
 // and the GAE-lambda scan.  The forward is gm_policy_net.h's gp_forward_tile with each net's
 // activation code; sampling is gm_ac_net.h's ga_sample (both shared with gm_rollout's per-env
-// driver, gm_kernels.hip ac_rollout_driver).
+// driver, gm_rollout.h ac_rollout_driver).
 #pragma once
 #include "gm_ac_net.h"
 

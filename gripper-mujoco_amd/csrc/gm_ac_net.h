@@ -1,6 +1,6 @@
 // gm_ac_net.h -- on-device PPO actor-critic: GaNet / GaArgs, the sampler ga_sample and the
 // one-env critic ga_value_one (shared by gm_ac.hip's batched kernels and the rollout driver
-// in gm_kernels.hip).
+// in gm_rollout.h).
 //
 // Reference: rl/agents/PolicyGradient.py:449-552 MLPGaussianActor / MLPCritic /
 // MLPActorCriticPG.step and :1348-1386 Agent_PPO.select_action:

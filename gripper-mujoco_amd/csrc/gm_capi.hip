@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "gm_kernels.hip"
+#include "gm_env_kernels.hip"
 #include "gm_policy.hip"
 #include "gm_ac.hip"
 
@@ -190,7 +191,7 @@ hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, 
   // the full env-step (mode 0) runs in cost-sorted order and records each env's cost
   const int32_t* order = (mode == 0 && grid == c->n_envs) ? c->d_order.get() : nullptr;
   uint32_t* cost = (mode == 0 && grid == c->n_envs) ? c->d_cost.get() : nullptr;
-  // the chunked work queue (gm_chunkq.h, gm_kernels.hip chunked_env_steps): one workgroup per
+  // the chunked work queue (gm_chunkq.h, gm_rollout.h chunked_env_steps): one workgroup per
   // resident wave slot, each pulling env chunks until every env has finished
   const bool chunked = order && c->chunk > 0 && c->chunk_grid > 0 && dbg.phase == nullptr;
   GmChunkQ q{c->d_chunk_ctr, c->d_chunk_ring, c->d_chunk_carry, c->chunk_cap, chunked ? c->chunk : 0,

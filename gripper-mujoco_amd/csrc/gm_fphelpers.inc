@@ -1,4 +1,4 @@
-// Floating-point helpers, included twice by gm_kernels.hip: at file scope with FMA
+// Floating-point helpers, included twice by gm_real.h: at file scope with FMA
 // contraction off (everything the oracle must reproduce bit for bit: resets, spawns,
 // stepper, sensors, observations) and inside namespace gmf with contraction on (the
 // physics substep).  No include guard on purpose.

@@ -1,5 +1,5 @@
-// gm_newton.hip -- box-box collision and the constraint solve of the env-step kernel
-// (included by gm_kernels.hip after the kinematics / dynamics stages).
+// gm_newton.hip -- physics stage 3, the constraint solve of the env-step kernel (after the
+// smooth dynamics, gm_dynamics.h, and the collider, gm_collide.h).
 //
 // The constraint problem is MuJoCo's (mj_makeConstraint / mj_makeImpedance with the
 // mj_diagApprox regulariser, pyramidal cones), solved to its unique optimum by MuJoCo's
@@ -15,233 +15,13 @@
 // oracle/physics.c restates every function here operation for operation (the oracle's
 // lane emulation), so device and oracle agree bit for bit from the same state.
 
-// ------------------------------------------------------------ box-box (mjc_BoxBox)
-// Separating axes, then the face-clipped manifold (see oracle/physics.c bb_setup): the
-// face case keeps up to 8 of 24 candidates (incident vertices inside the reference face,
-// reference corners inside the incident face, edge crossings) below the reference face.
-#define BB_NCAND 24
-struct BBox {
-  int kind;                     // 0 none, 1 face, 2 edge
-  real n[3], pen, sgn;
-  real crf[3], ru[3], rv[3], hu, hv;
-  real V[4][3], cinc[3], ninc[3], pu[4], pv[4];
-};
+// SharedT: reads con, cbody, pair_off / pair_cnt, cdof, Hf / Hp / Ho / Hbb, frc, s.qpos, s.qvel,
+// s.qacc_warm, s.lock_*; writes lrow_*, nl, nefc, qacc, xs, Ma, Mv, go, res_valid, con's forces,
+// s.qacc_warm, s.newton_caps, work_nefc / work_newton and the union's nw, nw2, st, fs, dbg.
+#pragma once
+#include "gm_real.h"
 
-__device__ __forceinline__ void bb_setup(const GeomV& A, const GeomV& B, BBox& S, real* ea, real* eb, real* da,
-                                         real* db) {
-  S.kind = 0;
-  const real d[3] = {B.c[0] - A.c[0], B.c[1] - A.c[1], B.c[2] - A.c[2]};
-  real a[3][3], b[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int k = 0; k < 3; k++) { a[i][k] = A.R[3 * k + i]; b[i][k] = B.R[3 * k + i]; }
-  real Ca[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) Ca[i][j] = fabs(dot3(a[i], b[j]));
-  real best = 0;
-  int code = -1;
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const real rb = B.size[0] * Ca[i][0] + B.size[1] * Ca[i][1] + B.size[2] * Ca[i][2];
-    const real pen = (A.size[i] + rb) - fabs(dot3(d, a[i]));
-    if (pen < 0) return;
-    if (code < 0 || pen < best) { best = pen; code = i; }
-  }
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    const real ra = A.size[0] * Ca[0][j] + A.size[1] * Ca[1][j] + A.size[2] * Ca[2][j];
-    const real pen = (ra + B.size[j]) - fabs(dot3(d, b[j]));
-    if (pen < 0) return;
-    if (pen < best) { best = pen; code = 3 + j; }
-  }
-  real ebest = 0, eL[3] = {0, 0, 0};
-  int ecode = -1;
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      real L[3];
-      cross3(L, a[i], b[j]);
-      const real len2 = dot3(L, L);
-      const real len = sqrt_n(len2);
-      if (len < 1e-6) continue;
-      const real il = rsq_n(len2);
-      L[0] *= il; L[1] *= il; L[2] *= il;
-      const real ra = A.size[0] * fabs(dot3(a[0], L)) + A.size[1] * fabs(dot3(a[1], L)) + A.size[2] * fabs(dot3(a[2], L));
-      const real rb = B.size[0] * fabs(dot3(b[0], L)) + B.size[1] * fabs(dot3(b[1], L)) + B.size[2] * fabs(dot3(b[2], L));
-      const real pen = (ra + rb) - fabs(dot3(d, L));
-      if (pen < 0) return;
-      if (ecode < 0 || pen < ebest) { ebest = pen; ecode = 3 * i + j; eL[0] = L[0]; eL[1] = L[1]; eL[2] = L[2]; }
-    }
-  if (ecode >= 0 && ebest < 0.95 * best) {
-    const int i = ecode / 3, j = ecode % 3;
-    real L[3] = {eL[0], eL[1], eL[2]};
-    if (dot3(d, L) < 0) { L[0] = -L[0]; L[1] = -L[1]; L[2] = -L[2]; }
-    S.kind = 2;
-    S.pen = ebest;
-    S.n[0] = L[0]; S.n[1] = L[1]; S.n[2] = L[2];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { ea[k] = A.c[k]; eb[k] = B.c[k]; }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      da[k] = (i == 0) ? a[0][k] : (i == 1) ? a[1][k] : a[2][k];
-      db[k] = (j == 0) ? b[0][k] : (j == 1) ? b[1][k] : b[2][k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      if (k != i) {
-        const real s = dot3(a[k], L) >= 0 ? A.size[k] : -A.size[k];
-#pragma unroll
-        for (int t = 0; t < 3; t++) ea[t] += s * a[k][t];
-      }
-      if (k != j) {
-        const real s = dot3(b[k], L) >= 0 ? -B.size[k] : B.size[k];
-#pragma unroll
-        for (int t = 0; t < 3; t++) eb[t] += s * b[k][t];
-      }
-    }
-    return;
-  }
-  const bool ref_is_a = code < 3;
-  const int ri = ref_is_a ? code : code - 3;
-  // reference / incident box data by selection (no pointer to a register array)
-  real rc[3], ic[3], rs[3], is[3], ra[3][3], ia[3][3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    rc[k] = ref_is_a ? A.c[k] : B.c[k];
-    ic[k] = ref_is_a ? B.c[k] : A.c[k];
-    rs[k] = ref_is_a ? A.size[k] : B.size[k];
-    is[k] = ref_is_a ? B.size[k] : A.size[k];
-#pragma unroll
-    for (int t = 0; t < 3; t++) { ra[k][t] = ref_is_a ? a[k][t] : b[k][t]; ia[k][t] = ref_is_a ? b[k][t] : a[k][t]; }
-  }
-  real rax[3], rau[3], rav[3];
-  const int ui = (ri + 1) % 3, vi = (ri + 2) % 3;
-#pragma unroll
-  for (int t = 0; t < 3; t++) {
-    rax[t] = ri == 0 ? ra[0][t] : ri == 1 ? ra[1][t] : ra[2][t];
-    rau[t] = ui == 0 ? ra[0][t] : ui == 1 ? ra[1][t] : ra[2][t];
-    rav[t] = vi == 0 ? ra[0][t] : vi == 1 ? ra[1][t] : ra[2][t];
-  }
-  const real rsi = ri == 0 ? rs[0] : ri == 1 ? rs[1] : rs[2];
-  const real dd[3] = {ic[0] - rc[0], ic[1] - rc[1], ic[2] - rc[2]};
-  const real s0 = dot3(dd, rax) >= 0 ? 1.0 : -1.0;
-  S.kind = 1;
-  S.pen = best;
-  S.sgn = ref_is_a ? 1.0 : -1.0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) S.n[k] = s0 * rax[k];
-#pragma unroll
-  for (int k = 0; k < 3; k++) { S.crf[k] = rc[k] + rsi * S.n[k]; S.ru[k] = rau[k]; S.rv[k] = rav[k]; }
-  S.hu = ui == 0 ? rs[0] : ui == 1 ? rs[1] : rs[2];
-  S.hv = vi == 0 ? rs[0] : vi == 1 ? rs[1] : rs[2];
-  int jm = 0;
-  real bm = fabs(dot3(S.n, ia[0]));
-#pragma unroll
-  for (int j = 1; j < 3; j++) { const real v = fabs(dot3(S.n, ia[j])); if (v > bm) { bm = v; jm = j; } }
-  real iaj[3], ie1[3], ie2[3];
-  const int e1 = (jm + 1) % 3, e2 = (jm + 2) % 3;
-#pragma unroll
-  for (int t = 0; t < 3; t++) {
-    iaj[t] = jm == 0 ? ia[0][t] : jm == 1 ? ia[1][t] : ia[2][t];
-    ie1[t] = e1 == 0 ? ia[0][t] : e1 == 1 ? ia[1][t] : ia[2][t];
-    ie2[t] = e2 == 0 ? ia[0][t] : e2 == 1 ? ia[1][t] : ia[2][t];
-  }
-  const real isj = jm == 0 ? is[0] : jm == 1 ? is[1] : is[2];
-  const real h1 = e1 == 0 ? is[0] : e1 == 1 ? is[1] : is[2];
-  const real h2 = e2 == 0 ? is[0] : e2 == 1 ? is[1] : is[2];
-  const real sj = dot3(S.n, iaj) >= 0 ? -1.0 : 1.0;
-#pragma unroll
-  for (int k = 0; k < 3; k++) { S.ninc[k] = sj * iaj[k]; S.cinc[k] = ic[k] + isj * S.ninc[k]; }
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const real su = (q == 1 || q == 2) ? 1.0 : -1.0, sv = (q >= 2) ? 1.0 : -1.0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) S.V[q][k] = S.cinc[k] + (su * h1) * ie1[k] + (sv * h2) * ie2[k];
-    const real r[3] = {S.V[q][0] - S.crf[0], S.V[q][1] - S.crf[1], S.V[q][2] - S.crf[2]};
-    S.pu[q] = dot3(r, S.ru);
-    S.pv[q] = dot3(r, S.rv);
-  }
-}
-// face candidate i (see oracle/physics.c bb_face_cand); i compile-time after unrolling
-__device__ __forceinline__ int bb_face_cand(const BBox& S, int i, real* P, real& depth) {
-  if (i < 4) {
-    if (!(fabs(S.pu[i]) <= S.hu && fabs(S.pv[i]) <= S.hv)) return 0;
-    P[0] = S.V[i][0]; P[1] = S.V[i][1]; P[2] = S.V[i][2];
-  } else if (i < 8) {
-    const int m = i - 4;
-    const real cu = (m == 1 || m == 2) ? S.hu : -S.hu, cv = (m >= 2) ? S.hv : -S.hv;
-    real sgn_min = 0, sgn_max = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int q1 = (q + 1) & 3;
-      const real ex = S.pu[q1] - S.pu[q], ey = S.pv[q1] - S.pv[q];
-      const real cr = ex * (cv - S.pv[q]) - ey * (cu - S.pu[q]);
-      if (q == 0) { sgn_min = cr; sgn_max = cr; }
-      else { sgn_min = fmin(sgn_min, cr); sgn_max = fmax(sgn_max, cr); }
-    }
-    if (!(sgn_min >= 0 || sgn_max <= 0)) return 0;
-    real Q[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) Q[k] = S.crf[k] + cu * S.ru[k] + cv * S.rv[k];
-    const real den = dot3(S.ninc, S.n);
-    if (fabs(den) < 1e-12) return 0;
-    const real r[3] = {S.cinc[0] - Q[0], S.cinc[1] - Q[1], S.cinc[2] - Q[2]};
-    const real t = div_n(dot3(S.ninc, r), den);
-#pragma unroll
-    for (int k = 0; k < 3; k++) P[k] = Q[k] + t * S.n[k];
-  } else {
-    const int q = (i - 8) >> 2, m = (i - 8) & 3;
-    const int q1 = (q + 1) & 3;
-    const real du = S.pu[q1] - S.pu[q], dv = S.pv[q1] - S.pv[q];
-    real t;
-    if (m < 2) {
-      if (fabs(du) < 1e-15) return 0;
-      const real bound = m == 0 ? -S.hu : S.hu;
-      t = div_n(bound - S.pu[q], du);
-      if (!(t > 0 && t < 1)) return 0;
-      const real vt = S.pv[q] + t * dv;
-      if (!(fabs(vt) < S.hv)) return 0;
-    } else {
-      if (fabs(dv) < 1e-15) return 0;
-      const real bound = m == 2 ? -S.hv : S.hv;
-      t = div_n(bound - S.pv[q], dv);
-      if (!(t > 0 && t < 1)) return 0;
-      const real ut = S.pu[q] + t * du;
-      if (!(fabs(ut) < S.hu)) return 0;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) P[k] = S.V[q][k] + t * (S.V[q1][k] - S.V[q][k]);
-  }
-  const real r[3] = {S.crf[0] - P[0], S.crf[1] - P[1], S.crf[2] - P[2]};
-  depth = dot3(S.n, r);
-  return depth > 0;
-}
-__device__ __forceinline__ void bb_face_hit(const BBox& S, const real* P, real depth, Hit& h) {
-  h.dist = -depth;
-#pragma unroll
-  for (int k = 0; k < 3; k++) { h.pos[k] = P[k] + (0.5 * depth) * S.n[k]; h.n[k] = S.sgn * S.n[k]; }
-}
-__device__ __forceinline__ int bb_edge_hit(const BBox& S, const real* ea, const real* eb, const real* da,
-                                           const real* db, Hit& h) {
-  const real w[3] = {ea[0] - eb[0], ea[1] - eb[1], ea[2] - eb[2]};
-  const real b = dot3(da, db), dd = dot3(da, w), e = dot3(db, w);
-  const real den = 1.0 - b * b;
-  if (!(den > 1e-12)) return 0;
-  const real s = div_n(b * e - dd, den), t = div_n(e - b * dd, den);
-  h.dist = -S.pen;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const real pa = ea[k] + s * da[k], pb = eb[k] + t * db[k];
-    h.pos[k] = 0.5 * (pa + pb);
-    h.n[k] = S.n[k];
-  }
-  return 1;
-}
-
+GM_PHYSICS_BEGIN
 // ------------------------------------------------------------ constraint rows
 // the solimp sigmoid's general power (cold on the canonical model): one pow pair serves
 // both halves; outlined so the inlined fast path stays small
@@ -618,9 +398,6 @@ __device__ void constraint_setup(SharedT<CL>& S, const gm_model* __restrict__ m,
   if (lane < GM_MAX_LOCK) { R.lD = S.lrow_D[lane]; R.laref = S.lrow_aref[lane]; R.ldof = S.lrow_dof[lane]; }
   if (lane >= nl) { R.lD = 0; R.laref = 0; R.ldof = 0; }
   if (lane == 0) S.nefc = nl + 4 * S.ncon;
-#ifdef GM_PHASE_SPLIT_SETUP
-  PH(15);   // developer split: lock rows
-#endif
   if constexpr (DUO) {
     // formed by the helper wave after its collider (duo_helper), read after the barrier
     const DuoRows<CL>* dr = duo_rows<CL>();
@@ -641,9 +418,6 @@ __device__ void constraint_setup(SharedT<CL>& S, const gm_model* __restrict__ m,
     jql = (lane < nl) ? qw - R.laref : 0.0;
   }
   GM_WAVE_SYNC();
-#ifdef GM_PHASE_SPLIT_SETUP
-  PH(11);   // developer split: the contact rows
-#endif
 }
 
 // J v - aref for every row at the dof vector v (LDS); into jr (contact) / jl (lock)
@@ -1260,11 +1034,7 @@ __device__ void newton_point(SharedT<CL>& S, const gm_model* __restrict__ m, con
     S.xs[bi == 0 ? T->dof_base : T->dof_obj + bi - 1] = y;
   }
   GM_WAVE_SYNC();
-#ifdef GM_PHASE_SPLIT_NARROW
-  PH(14);
-#else
   PH(24);
-#endif
 }
 
 // mj_solNewton restated (oracle newton_solve): warm start, Newton point on the active
@@ -1278,19 +1048,12 @@ __device__ __forceinline__ void newton_solve(SharedT<CL>& S, const gm_model* __r
   real jq[4], jql;
   bool obj_only;
   constraint_setup<CL, CAL, DUO>(S, m, T, lane, R, jq, jql, obj_only, prof);
-#ifdef GM_PHASE_SPLIT_SETUP
-  if (prof) t0 = clock64();   // the split phases above were charged inside; the rest: contact rows
-#endif
   PH(11);
   const int ncon = S.ncon, nl = S.nl, nv = T->nv;
   const bool clane = lane < ncon;
   if (lane < nv) S.qacc[lane] = S.s.qacc_warm[lane];
   GM_WAVE_SYNC();
-#ifdef GM_PHASE_SPLIT_NARROW
-  PH(11);
-#else
   PH(12);
-#endif
   int it = 0, nls = 0;
   bool capped = true;   // no Newton point accepted within GM_NEWTON_MAXIT iterations
   bool ls_cap = false;  // a line search ran GM_NEWTON_MAXLS evaluations without settling
@@ -1604,3 +1367,5 @@ __device__ __forceinline__ void euler_damping(SharedT<CL>& S, const GmTopo* __re
   const real sch = euler_factor<CL>(S, T, h, lane, L, lb, invd);
   euler_solve<CL>(S, T, h, lane, L, lb, invd, sch);
 }
+GM_PHYSICS_END
+using gmf::newton_solve, gmf::euler_factor, gmf::contact_rows, gmf::duo_rows, gmf::DuoRows;

@@ -130,7 +130,7 @@ __device__ __forceinline__ int gp_forward_tile(const float* __restrict__ obs, fl
   return cur;
 }
 
-// The same forward for ONE env on its own wave (gm_rollout's drivers, gm_kernels.hip
+// The same forward for ONE env on its own wave (gm_rollout's drivers, gm_rollout.h
 // chunked_env_steps and ac_rollout_driver): the tile form's MFMA tiles with this env in row 0
 // and zero rows below it.  MFMA rows are independent, so every output is bit for bit the tile
 // form's for the same observation.  obs: the env's observation (read with agent-scope loads,
@@ -186,7 +186,7 @@ __device__ __forceinline__ int gp_forward_one(const float* obs, float* copy, con
   return cur;
 }
 
-// select_action for ONE env on its own wave (gm_rollout's policy driver, gm_kernels.hip
+// select_action for ONE env on its own wave (gm_rollout's policy driver, gm_rollout.h
 // chunked_env_steps): the ReLU forward, then lane 0 chooses.  act: 2 x GP_ROW floats of LDS
 // scratch.  Returns the action on every lane.
 __device__ __forceinline__ int gp_select_one(const float* obs, const float* __restrict__ params, const GpNet& P,

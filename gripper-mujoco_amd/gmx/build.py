@@ -11,7 +11,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-munsafe-fp-atomics",
          "-ffp-contract=off",
-         # MachineLICM off: in the outlined substep loop (gm_kernels.hip substep_loop) it
+         # MachineLICM off: in the outlined substep loop (gm_substep.h substep_loop) it
          # hoists constant materialisations out of the loop and the body then spills
          "-mllvm", "-disable-machine-licm"]
 

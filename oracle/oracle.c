@@ -1096,7 +1096,7 @@ void or_set_action(or_env* e, const float* a) {
 void or_set_discrete_action(or_env* e, int32_t a) { set_action(e, a, 0); }
 
 /* the rollout drivers' fractions for the env's current state (the device's driver_fraction,
- * gm_kernels.hip; test infrastructure): 0 scripted grasp mix, 1 uniform random (the counter
+ * gm_rollout.h; test infrastructure): 0 scripted grasp mix, 1 uniform random (the counter
  * hash), 3 grasp-lift-hold program (gm_state.h gm_program_fraction), 4 the program in 1
  * episode of 4 and the scripted mix otherwise; gid = the env's global id */
 void or_driver_actions(const or_env* e, int mode, uint64_t seed, float jitter, int64_t gid, float* out) {

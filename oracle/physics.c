@@ -5,7 +5,7 @@
  * restated (kinematics, composite rigid bodies, RNE bias, the Euler step with implicit
  * damping, collision, soft constraints, MuJoCo's Newton solver) -- written so that
  * every floating-point operation happens in the same order as in the device kernels
- * (gripper-mujoco_amd/csrc/gm_kernels.hip): where the device composes a finger chain by a
+ * (gripper-mujoco_amd/csrc gm_dynamics.h .. gm_integrate.h): where the device composes a finger chain by a
  * Hillis-Steele scan across a 16-lane DPP row, or sums a wave by an xor butterfly, this
  * file emulates that scan / butterfly lane by lane, so one substep from the same state
  * gives the same bits on both sides.  The algorithms are the reference's (MuJoCo's)
@@ -129,7 +129,7 @@ static double butterfly64(const double* v_in) {
 }
 
 /* =====================================================================
- * kinematics (mj_kinematics + mj_comPos restated; the device's gm_kernels.hip kinematics)
+ * kinematics (mj_kinematics + mj_comPos restated; the device's gm_dynamics.h kinematics)
  * ===================================================================== */
 static void fk(or_env* e) {
   const gm_model* m = &e->m;

@@ -1,4 +1,4 @@
-"""The chunked env-step dispatch (gm_kernels.hip chunked_env_steps: a persistent work queue
+"""The chunked env-step dispatch (gm_rollout.h chunked_env_steps: a persistent work queue
 whose envs yield to envs with more work left and resume on another wave of their XCD) must
 give bit for bit the one-shot kernel's results: the same substeps on the same state in the
 same order.  Each case steps two contexts of the same batch -- one-shot

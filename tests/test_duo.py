@@ -1,6 +1,6 @@
 """DUO workgroups (gm_step_kernel<CL, false, true>): for batches whose envs all fit
 resident with two waves each, the second wave of an env's workgroup runs the collider
-while the first forms the inertia and forces (gm_kernels.hip physics_substep_body /
+while the first forms the inertia and forces (gm_substep.h physics_substep_body / gm_kernels.hip
 duo_helper).  The same code runs on the same LDS image in the same order per env, so the
 results must equal the one-wave kernel's bit for bit: checked on grasp rollouts (scripted
 mix, mixed objects, cylinder) through the per-step API in both dispatch modes (chunked and

@@ -242,7 +242,7 @@ def test_program_rollout_equals_per_step_api_through_the_lift(gm):
 
 @pytest.mark.gpu
 def test_work_queue_claims_never_park_tiny_grid_4096(gm):
-    """Regression test of the work queue's claim protocol (claim_bucket, gm_kernels.hip): a
+    """Regression test of the work queue's claim protocol (claim_bucket / cq_claim, gm_chunkq.h): a
     4096-env rollout on a deliberately tiny persistent grid (16 workgroups) with the hand-off
     heavy knobs -- thousands of yields and resumptions, every wave contending for the same
     bucket slots -- equals the per-step calls bit for bit, and no claim parks: a claimed slot

@@ -1,4 +1,4 @@
-"""Developer model of the chunked env-step's dispatch (gm_kernels.hip chunked_env_steps):
+"""Developer model of the chunked env-step's dispatch (gm_rollout.h chunked_env_steps):
 list scheduling of n env-steps on m resident wave slots in G XCD groups, envs started in
 descending predicted cost, a running env yielding every `every` substeps when the next
 unstarted env (margin) or the best yielded env of its group (cmargin) has clearly more

@@ -7,7 +7,12 @@ Compare two trees ("PPO actor-critic rollout"):
   python -c "import __graft_entry__ as g; g.build()"        # in each tree
   python tools/step_kernel_resources.py --label parent --label this --out profiles/ac_rollout_step_kernel_resources.json \\
          <parent tree>/gripper-mujoco_amd/lib/obj/gm_capi.hip.o gripper-mujoco_amd/lib/obj/gm_capi.hip.o
-The script exits 1 when the last object's LDS or scratch exceeds the first's for any kernel."""
+The script exits 1 when the last object's LDS or scratch exceeds the first's for any kernel.
+
+Prove that a change which only moves source text left the device code alone:
+  python tools/step_kernel_resources.py --same-code <parent>/.../obj/gm_capi.hip.o gripper-mujoco_amd/lib/obj/gm_capi.hip.o
+compares the .text, .rodata and .note sections of the two gfx950 code objects byte for byte
+(the symbol tables may be ordered differently; nothing else may) and exits 1 on a difference."""
 import argparse
 import json
 import os
@@ -18,6 +23,7 @@ import tempfile
 
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+SECTIONS = (".text", ".rodata", ".note")
 FUNCS = ("ac_rollout_driver", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel", "gm_policy_kernel",
          "substep_loop", "reset_env", "driver_actions")
 
@@ -28,9 +34,7 @@ def tool(name, *args):
 
 def usage(obj):
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat"), os.path.join(d, "co")
-        tool("llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj)
-        tool("clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={fat}", f"--output={co}")
+        co = code_object(obj, d)
         notes = tool("llvm-readelf", "--notes", co)
         syms = tool("llvm-readelf", "-sW", co)
     size = {}
@@ -57,7 +61,57 @@ def usage(obj):
     return dict(kernels=kernels, functions=funcs)
 
 
+def code_object(obj, d):
+    fat, co = os.path.join(d, "fat"), os.path.join(d, "co")
+    tool("llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj)
+    tool("clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={fat}", f"--output={co}")
+    return co
+
+
+def same_code(a, b):
+    """Byte comparison of the code-bearing sections of two objects' gfx950 code objects; a report
+    line per section, the first differing section with the function its first differing byte is in."""
+    lines, first = [], None
+    with tempfile.TemporaryDirectory() as d:
+        cos = []
+        for i, obj in enumerate((a, b)):
+            os.mkdir(os.path.join(d, str(i)))
+            cos.append(code_object(obj, os.path.join(d, str(i))))
+        for sec in SECTIONS:
+            data = []
+            for i, co in enumerate(cos):
+                out = os.path.join(d, str(i), "sec")
+                tool("llvm-objcopy", "--dump-section", f"{sec}={out}", co)
+                with open(out, "rb") as f:
+                    data.append(f.read())
+            same = data[0] == data[1]
+            lines.append(f"{sec:8s} {len(data[0]):9d} B  {len(data[1]):9d} B  {'identical' if same else 'DIFFERENT'}")
+            if same or first is not None:
+                continue
+            off = next((k for k, (x, y) in enumerate(zip(*data)) if x != y), min(map(len, data)))
+            first = f"first difference: {sec} + {off:#x}"
+            if sec == ".text":   # the function of the first object that holds that byte
+                base = int(re.search(r"\] \.text\s+\S+\s+([0-9a-f]+)", tool("llvm-readelf", "-SW", cos[0])).group(1), 16)
+                for f in (ln.split() for ln in tool("llvm-readelf", "-sW", cos[0]).splitlines()):
+                    if len(f) >= 8 and f[3] == "FUNC" and int(f[1], 16) <= base + off < int(f[1], 16) + int(f[2]):
+                        first += f" in {f[7]}"
+                        break
+    return lines, first
+
+
 def main():
+    if "--same-code" in sys.argv[1:]:
+        ap = argparse.ArgumentParser()
+        ap.add_argument("--same-code", nargs=2, metavar=("PARENT_OBJ", "OBJ"), required=True)
+        ap.add_argument("--out", help="append the report to this file")
+        a = ap.parse_args()
+        lines, first = same_code(*a.same_code)
+        text = "\n".join([f"{a.same_code[0]} vs {a.same_code[1]}", *lines, first or "same code"]) + "\n"
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(text)
+        print(text, end="")
+        return 1 if first else 0
     ap = argparse.ArgumentParser()
     ap.add_argument("--label", action="append", default=[])
     ap.add_argument("--out")
