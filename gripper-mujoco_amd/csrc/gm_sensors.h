@@ -51,9 +51,20 @@ __device__ float s_normalise(const gm_sensor& ss, float v) {
   if (v < -ss.normalise) return -1.0f;
   return v / ss.normalise;
 }
+// Box-Muller's z0 = mag * cos(2 pi u2) + mu (mjclass.h:211-212).  log and cos of the float
+// argument are taken in fp64 and rounded to float: the float function's correctly rounded value,
+// whichever math library is underneath (ocml's logf / cosf are within an ulp of it, which the
+// smallest accepted u1, log = -15.9, turns into two ulps of the noise value).  One outlined
+// copy: s_noise is inlined at fifteen call sites.
+__device__ __noinline__ float gauss_z0(float noise_std, float u1, float u2, float mu) {
+  const float two_pi = (float)(2.0 * 3.14159265358979323846);
+  const float lg = (float)log((double)u1);
+  const float cs = (float)gm_cos((double)(two_pi * u2));
+  const float mag = (float)(noise_std * sqrt(-2.0 * (double)lg));
+  return mag * cs + mu;
+}
 __device__ float s_noise(GmEnvHot& s, const gm_sensor& ss, int slot, float value, int i) {
   if (!ss.use_noise) return value;
-  const float two_pi = (float)(2.0 * 3.14159265358979323846);
   const float eps = 1.1920928955078125e-07f;
   float mu = s.rand_mu[slot][i - 1];
   if (ss.noise_std < eps) {
@@ -63,8 +74,7 @@ __device__ float s_noise(GmEnvHot& s, const gm_sensor& ss, int slot, float value
     float u1, u2;
     do { u1 = unif01(s.rng); } while (u1 <= eps);
     u2 = unif01(s.rng);
-    float mag = (float)(ss.noise_std * sqrt(-2.0 * (double)logf(u1)));
-    float z0 = mag * cosf(two_pi * u2) + mu;
+    float z0 = gauss_z0(ss.noise_std, u1, u2, mu);
     value += z0;
   }
   if (value > 1) value = 1;

@@ -562,8 +562,11 @@ static float s_noise(or_env* e, const gm_sensor* s, int slot, float value, int i
     float u1, u2;
     do { u1 = unif01(&e->rng); } while (u1 <= eps);
     u2 = unif01(&e->rng);
-    float mag = (float)(s->noise_std * sqrt(-2.0 * (double)logf(u1)));
-    float z0 = mag * cosf(two_pi * u2) + mu;
+    /* log and cos of the float argument in fp64, rounded to float (as gm_sensors.h's s_noise) */
+    const float lg = (float)log((double)u1);
+    const float cs = (float)gm_cos((double)(two_pi * u2));
+    float mag = (float)(s->noise_std * sqrt(-2.0 * (double)lg));
+    float z0 = mag * cs + mu;
     value += z0;
   }
   if (value > 1) value = 1;
