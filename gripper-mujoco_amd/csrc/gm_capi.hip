@@ -21,6 +21,7 @@
 #include "gm_kernels.hip"
 #include "gm_env_kernels.hip"
 #include "gm_policy.hip"
+#include "gm_replay.hip"
 #include "gm_ac.hip"
 
 // calibration translation unit (gm_calib.hip)
@@ -1291,6 +1292,9 @@ struct gm_policy {
   DevBuf<float> d_q;
   DevBuf<float> d_eps;         // gm_policy_rollout's exploration thresholds, one per env-step
   int eps_cap = 0;
+  std::vector<int32_t> sizes;  // the layer widths (gm_policy_set_params repacks with them)
+  int64_t total = 0;           // packed floats
+  DevBuf<GrArgs> d_replay;     // gm_policy_rollout_replay's launch arguments
 };
 
 static int64_t policy_layout(const int32_t* sizes, int n_sizes, GpNet* net) {
@@ -1355,7 +1359,10 @@ int gm_policy_create(gm_ctx* c, const int32_t* sizes, int n_sizes, const float* 
   gm_policy* p = new gm_policy;
   p->ctx = c;
   p->net = P;
+  p->sizes.assign(sizes, sizes + n_sizes);
+  p->total = total;
   hipError_t e = p->d_params.alloc((size_t)total);
+  if (e == hipSuccess) e = p->d_replay.alloc(1);
   if (e == hipSuccess) e = p->d_actions.alloc((size_t)c->n_envs);
   if (e == hipSuccess) e = p->d_q.alloc((size_t)c->n_envs * c->cfg.n_actions);
   if (e == hipSuccess)
@@ -1389,10 +1396,62 @@ int gm_policy_act(gm_policy* p, float eps, uint64_t seed, uint64_t decision) {
   return gm_set_discrete_action(c, p->d_actions, 1);
 }
 
-int gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed, uint64_t decision0,
-                      int max_episode_steps, gm_episode_end* records) {
+int gm_policy_set_params(gm_policy* p, const float* params) {
+  if (!p || !p->ctx || !params) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<float> packed((size_t)p->total);
+  gm_policy_pack(p->sizes.data(), (int)p->sizes.size(), params, packed.data());
+  return stage_upload(c, p->d_params, packed.data(), sizeof(float) * (size_t)p->total);
+}
+
+}  // extern "C"
+
+// the device-side view of a caller's replay memory for a call of n_steps env-steps that starts
+// after row0 pushed transitions; false (with the message what) for a buffer the call cannot use
+static bool replay_args(gm_ctx* c, const gm_replay* r, int64_t row0, int n_steps, const char* what, GrArgs& R) {
+  if (!r || r->capacity < 1 || !r->state || !r->action || !r->next_state || !r->reward || !r->end || row0 < 0) {
+    fail(c, GM_E_ARG, std::string(what) + ": incomplete replay memory or negative row0");
+    return false;
+  }
+  if ((int64_t)n_steps * c->n_envs > r->capacity) {
+    fail(c, GM_E_ARG, std::string(what) + ": " + std::to_string(n_steps) + " env-steps of " + std::to_string(c->n_envs) +
+                          " envs would write a row of the replay memory twice (capacity " +
+                          std::to_string((long long)r->capacity) + ")");
+    return false;
+  }
+  R = GrArgs{r->state, r->action, r->next_state, r->reward, r->end, (long long)r->capacity,
+             (long long)(row0 % r->capacity), c->cfg.n_obs, 0};
+  return true;
+}
+// a thread-per-element kernel over the envs' observations on the context's stream
+template <class K, class... A>
+static hipError_t launch_per_obs_element(const gm_ctx* c, long long n, K kernel, const A&... args) {
+  const int threads = 256;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), 0, c->stream, args...);
+  return hipGetLastError();
+}
+static int policy_push(gm_policy* p, const gm_replay* r, int64_t row0, int max_ep, bool begin) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  GrArgs R;
+  if (!replay_args(c, r, row0, 1, begin ? "gm_policy_push_begin" : "gm_policy_push_end", R)) return GM_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  const long long n = (long long)c->n_envs * c->cfg.n_obs;
+  if (begin)
+    HIPCHK(c, launch_per_obs_element(c, n, gm_replay_push_begin_kernel, c->d_obs, p->d_actions, c->n_envs, R));
+  else
+    HIPCHK(c, launch_per_obs_element(c, n, gm_replay_push_end_kernel, c->d_obs, c->d_state, c->d_rew, c->d_done,
+                                     c->n_envs, max_ep, R));
+  return GM_OK;
+}
+// gm_policy_rollout, recording into r (from row0) when r is non-NULL
+static int policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed, uint64_t decision0,
+                          int max_episode_steps, gm_episode_end* records, const gm_replay* r, int64_t row0) {
   if (!p || !p->ctx || !eps || n_steps < 1) return GM_E_ARG;
   gm_ctx* c = p->ctx;
+  GrArgs R{};
+  if (r && !replay_args(c, r, row0, n_steps, "gm_policy_rollout_replay", R)) return GM_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   if (chunk_queue_on(c)) {
     if (n_steps > p->eps_cap) {
@@ -1403,18 +1462,88 @@ int gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed
       p->eps_cap = n_steps;
     }
     // eps is the caller's (pageable) array: the copy owns its bytes before the call returns
-    const int rc = stage_upload(c, p->d_eps, eps, sizeof(float) * (size_t)n_steps);
+    int rc = stage_upload(c, p->d_eps, eps, sizeof(float) * (size_t)n_steps);
+    if (rc == GM_OK && r) rc = stage_upload(c, p->d_replay, &R, sizeof(GrArgs));
     if (rc != GM_OK) return rc;
     GmRolloutJob job = rollout_job(c, n_steps, GM_DRV_DQN, seed, 0.0f, max_episode_steps, records);
     job.pparams = p->d_params;
     job.pnet = p->net;
     job.peps = p->d_eps;
     job.pdecision = decision0;
+    job.replay = r ? p->d_replay.get() : nullptr;
     return timed_launch(c, &job);
   }
   return per_step_rollout(
       c, n_steps, max_episode_steps, records,
-      [&](int k) { return gm_policy_act(p, eps[k], seed, decision0 + (uint64_t)k); }, [](int) { return (int)GM_OK; });
+      [&](int k) {
+        const int rc = gm_policy_act(p, eps[k], seed, decision0 + (uint64_t)k);
+        return rc == GM_OK && r ? gm_policy_push_begin(p, r, row0 + (int64_t)k * c->n_envs) : rc;
+      },
+      [&](int k) {
+        return r ? gm_policy_push_end(p, r, row0 + (int64_t)k * c->n_envs, max_episode_steps) : (int)GM_OK;
+      });
+}
+
+extern "C" {
+
+int gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed, uint64_t decision0,
+                      int max_episode_steps, gm_episode_end* records) {
+  return policy_rollout(p, n_steps, eps, seed, decision0, max_episode_steps, records, nullptr, 0);
+}
+
+int gm_policy_push_begin(gm_policy* p, const gm_replay* replay, int64_t row0) {
+  return policy_push(p, replay, row0, 0, true);
+}
+
+int gm_policy_push_end(gm_policy* p, const gm_replay* replay, int64_t row0, int max_episode_steps) {
+  return policy_push(p, replay, row0, max_episode_steps, false);
+}
+
+int gm_policy_rollout_replay(gm_policy* p, int n_steps, const float* eps, uint64_t seed, uint64_t decision0,
+                             int max_episode_steps, gm_episode_end* records, const gm_replay* replay, int64_t row0) {
+  if (p && p->ctx && !replay) return fail(p->ctx, GM_E_ARG, "gm_policy_rollout_replay: no replay memory");
+  return policy_rollout(p, n_steps, eps, seed, decision0, max_episode_steps, records, replay, row0);
+}
+
+int gm_replay_indices(int64_t size, int batch, uint64_t seed, uint64_t draw, int32_t* out) {
+  if (size < 1 || size > 0x7FFFFFFFll || batch < 0 || batch > size || !out) return GM_E_ARG;
+  const uint64_t key = gr_key(seed, draw);
+  for (int i = 0; i < batch; i++) out[i] = (int32_t)gr_index((uint64_t)size, key, (uint64_t)i);
+  return GM_OK;
+}
+
+int gm_replay_sample(gm_ctx* c, const gm_replay* replay, int64_t size, int batch, uint64_t seed, uint64_t draw,
+                     const gm_replay_batch* out) {
+  if (!c) return GM_E_ARG;
+  if (!replay || !replay->state || !replay->action || !replay->next_state || !replay->reward || !replay->end || !out ||
+      !out->state || !out->action || !out->next_state || !out->reward || !out->end || !out->index)
+    return fail(c, GM_E_ARG, "gm_replay_sample: incomplete replay memory or batch arrays");
+  if (size < 1 || size > replay->capacity || size > 0x7FFFFFFFll || batch < 1 || batch > size)
+    return fail(c, GM_E_ARG, "gm_replay_sample: batch " + std::to_string(batch) + " of " + std::to_string((long long)size) +
+                                 " stored transitions (capacity " + std::to_string((long long)replay->capacity) +
+                                 "): 1 <= batch <= size <= capacity expected");
+  HIPCHK(c, hipSetDevice(c->device));
+  const GrArgs R{replay->state, replay->action, replay->next_state, replay->reward, replay->end,
+                 (long long)replay->capacity, 0, c->cfg.n_obs, 0};
+  HIPCHK(c, launch_per_obs_element(c, (long long)batch * c->cfg.n_obs, gm_replay_sample_kernel, R, (long long)size,
+                                   batch, gr_key(seed, draw), *out));
+  return GM_OK;
+}
+
+int gm_policy_td_target(gm_policy* target, gm_policy* online, const gm_replay_batch* batch, int n, float gamma,
+                        int mask_terminal, float* y, float* next_value) {
+  if (!target || !target->ctx) return GM_E_ARG;
+  gm_ctx* c = target->ctx;
+  if (online && online->ctx != c) return fail(c, GM_E_ARG, "gm_policy_td_target: the two policies belong to different contexts");
+  if (!batch || !batch->next_state || !batch->reward || !batch->end || !y || n < 1)
+    return fail(c, GM_E_ARG, "gm_policy_td_target: incomplete batch (next_state, reward, end), no y or n < 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(gm_td_target_kernel, dim3((n + GP_TILE - 1) / GP_TILE), dim3(64), 0, c->stream, batch->next_state,
+                     batch->reward, batch->end, n, target->d_params, target->net,
+                     online ? online->d_params.get() : nullptr, online ? online->net : target->net, gamma,
+                     mask_terminal, y, next_value);
+  HIPCHK(c, hipGetLastError());
+  return GM_OK;
 }
 
 int gm_policy_read(gm_policy* p, int32_t* actions, float* q) {

@@ -7,6 +7,7 @@
 #include "gm_state.h"
 #include "gm_policy_net.h"
 #include "gm_ac_net.h"
+#include "gm_replay.h"
 
 #define GM_CQ_NB 16      // priority buckets per XCD
 // The job every env of a launch runs: `steps` env-steps in a row, each the per-step API's sequence:
@@ -36,6 +37,7 @@ struct GmRolloutJob {
   const float* peps;         // [steps] exploration threshold per env-step of the launch,
   uint64_t pdecision;        // the first env-step's decision index
   const GaArgs* ac;          // GM_DRV_AC: device copy of the launch's arguments
+  const GrArgs* replay;      // GM_DRV_DQN: device copy of the replay memory to record into (NULL: none)
 };
 struct GmChunkCarry {        // what a chunk hands the next besides the hot state
   int32_t sub_done, nsub;

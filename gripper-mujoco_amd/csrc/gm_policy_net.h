@@ -44,8 +44,9 @@ typedef float gp_f32x4 __attribute__((ext_vector_type(4)));
 // counter-based uniform in [0, 1) and integer draws for epsilon-greedy: splitmix64 of
 // (seed, global env id, decision index) -- one independent stream per env, so actions do
 // not depend on how envs are sharded (the reference draws from one numpy Generator per
-// agent, which a batched device policy cannot reproduce draw for draw)
-__device__ __forceinline__ uint64_t gp_mix(uint64_t z) {
+// agent, which a batched device policy cannot reproduce draw for draw); also the host's
+// (gm_replay_indices)
+__host__ __device__ __forceinline__ uint64_t gp_mix(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -57,11 +58,10 @@ __device__ __forceinline__ float gp_activate(float v, int code) {
   return code == GP_ACT_TANH ? tanhf(v) : fmaxf(v, 0.0f);
 }
 
-// softmax over the logits (nn.Softmax(dim=1)), then Agent_DQN.select_action: argmax (first
-// maximum, like torch's max on CPU) or, with probability eps, a uniform random action from
-// the env's own counter-based stream.  One lane, one env; q (may be NULL) gets the softmax.
-__device__ __forceinline__ int gp_choose(const float* x, int n_out, float eps, uint64_t seed, uint64_t decision,
-                                         uint64_t gid, float* q_out) {
+// softmax over the logits (nn.Softmax(dim=1)) and its argmax (first maximum, like torch's max
+// on CPU).  One lane, one row; q_out (may be NULL) gets the softmax, qbest_out (may be NULL)
+// its maximum.  Shared by select_action (gp_choose) and the TD target (gm_replay.hip).
+__device__ __forceinline__ int gp_softmax_argmax(const float* x, int n_out, float* q_out, float* qbest_out) {
   float m = x[0];
   for (int j = 1; j < n_out; j++) m = fmaxf(m, x[j]);
   float sum = 0.0f;
@@ -73,6 +73,14 @@ __device__ __forceinline__ int gp_choose(const float* x, int n_out, float eps, u
     if (q_out) q_out[j] = q;
     if (q > qbest) { qbest = q; best = j; }
   }
+  if (qbest_out) *qbest_out = qbest;
+  return best;
+}
+// Agent_DQN.select_action on the softmax: its argmax or, with probability eps, a uniform random
+// action from the env's own counter-based stream.  One lane, one env; q (may be NULL) gets the softmax.
+__device__ __forceinline__ int gp_choose(const float* x, int n_out, float eps, uint64_t seed, uint64_t decision,
+                                         uint64_t gid, float* q_out) {
+  int best = gp_softmax_argmax(x, n_out, q_out, nullptr);
   const uint64_t h1 = gp_mix(seed ^ gp_mix(gid * 0x100000001B3ull + decision));
   const uint64_t h2 = gp_mix(h1);
   const float u = (float)((h1 >> 40) * (1.0 / 16777216.0));   // 24-bit uniform in [0, 1)

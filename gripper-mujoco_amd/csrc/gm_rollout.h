@@ -9,6 +9,7 @@
 #include "gm_chunkq.h"
 #include "gm_policy_net.h"
 #include "gm_ac_net.h"
+#include "gm_replay.h"
 
 // ------------------------------ chunked env-step: the rollout job (its work queue: gm_chunkq.h)
 // the grasp program's inputs (gm_state.h gm_program_fraction) from an env's state and its
@@ -126,7 +127,8 @@ __device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restri
 // scratch: the union S.st.  (The begin of an env-step is in chunked_env_steps: a function cost a VGPR.)
 __device__ __forceinline__ int64_t rollout_gid(const GmRolloutJob& J, int env) { return J.sr.env_offset + env; }
 // End env-step k, after the epilogue: gm_autoreset_episodes on this env -- the episode-end
-// record, the actor-critic's trajectory record, then MjEnv.reset and the reset observation
+// record, the actor-critic's trajectory record or the DQN replay memory's second half (gm_replay.h
+// replay_record), then MjEnv.reset and the reset observation
 template <int CL>
 __device__ __forceinline__ void rollout_end_step(SharedT<CL>& S, GmEnvState* g, float* __restrict__ obs, int env,
                                                  int n_envs, const GmRolloutJob& J, int k, const gm_model* __restrict__ m,
@@ -139,6 +141,7 @@ __device__ __forceinline__ void rollout_end_step(SharedT<CL>& S, GmEnvState* g, 
   if (J.driver == GM_DRV_AC)
     ac_rollout_driver(1, J.ac, obs + (size_t)env * C->n_obs, env, n_envs, k, J.max_ep, rollout_gid(J, env),
                       reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
+  if (J.replay) replay_record(1, J.replay, obs + (size_t)env * C->n_obs, env, n_envs, k, end, &S.s.reward, lane);
   if (end) {
     GM_ENV_SYNC();   // lane 0's epilogue writes (RNG, counters) before every lane reads them
     const GmResetKeep keep{S.s.rng, S.s.old_x, S.s.old_y, S.s.old_z, S.s.episode + 1, S.s.newton_caps};
@@ -225,6 +228,7 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
           const int a = gp_select_one(o, J.pparams, J.pnet, J.peps[cr.step_idx], J.seed,
                                       J.pdecision + (uint64_t)cr.step_idx, (uint64_t)rollout_gid(J, env),
                                       reinterpret_cast<float*>(&S.st), lane);
+          if (J.replay) replay_record(0, J.replay, o, env, n_envs, cr.step_idx, a, nullptr, lane);
           if (lane == 0) {
             set_action_one(S.s, m, C, a, 0.0f);
             S.stp_fixed = 0;

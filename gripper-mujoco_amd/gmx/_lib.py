@@ -282,6 +282,13 @@ def _declare(lib):
         "gm_policy_act": (i32, [vp, C.c_float, C.c_uint64, C.c_uint64]),
         "gm_policy_read": (i32, [vp, i32p, f32p]),
         "gm_policy_rollout": (i32, [vp, i32, f32p, C.c_uint64, C.c_uint64, i32, vp]),
+        "gm_policy_set_params": (i32, [vp, f32p]),
+        "gm_policy_push_begin": (i32, [vp, vp, C.c_int64]),
+        "gm_policy_push_end": (i32, [vp, vp, C.c_int64, i32]),
+        "gm_policy_rollout_replay": (i32, [vp, i32, f32p, C.c_uint64, C.c_uint64, i32, vp, vp, C.c_int64]),
+        "gm_replay_indices": (i32, [C.c_int64, i32, C.c_uint64, C.c_uint64, i32p]),
+        "gm_replay_sample": (i32, [vp, vp, C.c_int64, i32, C.c_uint64, C.c_uint64, vp]),
+        "gm_policy_td_target": (i32, [vp, vp, vp, i32, C.c_float, i32, vp, vp]),
         "gm_ac_create": (i32, [vp, i32p, i32, i32p, i32, f32p, C.POINTER(vp)]),
         "gm_ac_destroy": (None, [vp]),
         "gm_ac_set_params": (i32, [vp, f32p]),

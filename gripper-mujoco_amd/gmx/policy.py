@@ -9,6 +9,14 @@ Mirrors the reference's policy side of the rollout:
     action with that probability, otherwise the argmax of the network output.
 The forward pass and the choice run in one HIP kernel (gm_policy_kernel, f32 MFMA) on
 the env's device observations and the chosen actions are applied on the device.
+
+The data plumbing of training sits next to it, on the device too:
+  - ReplayMemory (DQN.py:11-62) as ReplayBuffer, pushed by DevicePolicy.push_begin / push_end
+    around an env-step or inside the fused launch (rollout(replay=buf)), sampled without
+    replacement by ReplayBuffer.sample;
+  - optimise_model's TD target (DQN.py:294-315), plain or double, as DevicePolicy.td_target.
+There is no trainer here: loss, backward, optimiser and the soft target update are the user's
+torch code, which hands new weights back with DevicePolicy.set_params().
 """
 from __future__ import annotations
 
@@ -20,6 +28,52 @@ import numpy as np
 from ._lib import load_library
 
 CANONICAL_HIDDEN = (150, 100, 50)
+
+_M64 = (1 << 64) - 1
+
+
+def _mix(z):
+    """gp_mix (csrc/gm_policy_net.h): splitmix64's finaliser on uint64 arrays."""
+    z = np.asarray(z, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def replay_indices(size: int, batch: int, seed: int = 0, draw: int = 0) -> np.ndarray:
+    """The numpy mirror of gm_replay_indices (csrc/gm_replay.h gr_index): `batch` distinct rows of
+    [0, size) -- index i is the image of i under a 4-round balanced Feistel network over the
+    smallest even bit count b with 2^b >= size, keyed by (seed, draw), cycle-walked into range."""
+    size, batch = int(size), int(batch)
+    if size < 1 or not 0 <= batch <= size:
+        raise ValueError(f"0 <= batch <= size and size >= 1 expected, got batch {batch}, size {size}")
+    h = 0
+    while (1 << (2 * h)) < size:
+        h += 1
+    mask = np.uint64((1 << h) - 1)
+    sh = np.uint64(h)
+    key = _mix(np.uint64(int(seed) & _M64) ^ _mix(np.uint64(int(draw) & _M64)))
+    x = np.arange(batch, dtype=np.uint64)
+    walk = np.ones(batch, dtype=bool)
+    while walk.any():
+        L, R = x[walk] >> sh, x[walk] & mask
+        for r in range(4):
+            with np.errstate(over="ignore"):
+                f = _mix(key + np.uint64(((r + 1) * 0xD1B54A32D192ED03) & _M64) + R) & mask
+            L, R = R, L ^ f
+        x[walk] = (L << sh) | R
+        walk = x >= np.uint64(size)
+    return x.astype(np.int32)
+
+
+def ring_rows(row0: int, n_steps: int, n_envs: int, capacity: int) -> np.ndarray:
+    """[n_steps, n_envs] ring rows a call writes that starts after row0 pushed transitions: env e
+    at env-step k goes to (row0 + k * n_envs + e) % capacity (include/gripper_mi355x.h gm_replay)."""
+    if n_steps * n_envs > capacity:
+        raise ValueError("the call would write a row twice")
+    return (int(row0) + np.arange(n_steps * n_envs, dtype=np.int64).reshape(n_steps, n_envs)) % int(capacity)
 
 
 def eps_threshold(decay_num: int, eps_start: float = 0.9, eps_end: float = 0.05, eps_decay: int = 1000) -> float:
@@ -81,6 +135,81 @@ def pack(sizes, params) -> np.ndarray:
     return out
 
 
+class Replay(C.Structure):
+    """gm_replay (include/gripper_mi355x.h)."""
+    _fields_ = [("capacity", C.c_int64), ("state", C.c_void_p), ("action", C.c_void_p), ("next_state", C.c_void_p),
+                ("reward", C.c_void_p), ("end", C.c_void_p)]
+
+
+class ReplayBatch(C.Structure):
+    """gm_replay_batch (include/gripper_mi355x.h)."""
+    _fields_ = [("state", C.c_void_p), ("action", C.c_void_p), ("next_state", C.c_void_p), ("reward", C.c_void_p),
+                ("end", C.c_void_p), ("index", C.c_void_p)]
+
+
+def _batch_struct(batch: dict) -> ReplayBatch:
+    b = ReplayBatch()
+    for name, _ in ReplayBatch._fields_:
+        t = batch.get(name)
+        setattr(b, name, t.data_ptr() if t is not None else None)
+    return b
+
+
+class ReplayBuffer:
+    """ReplayMemory (rl/agents/DQN.py:11-62) as torch tensors on the env's device in gm_replay's
+    layout: a ring of `capacity` transitions, `pushed` counting every transition ever written."""
+
+    def __init__(self, env, capacity: int):
+        import torch
+        self.env = env
+        self.capacity = int(capacity)
+        if self.capacity < env.n_envs:
+            raise ValueError(f"capacity {self.capacity} holds less than one env-step of {env.n_envs} envs")
+        self.pushed = 0
+        dev = f"cuda:{env.device}"
+        f = dict(dtype=torch.float32, device=dev)
+        self.state = torch.zeros((self.capacity, env.n_obs), **f)
+        self.action = torch.zeros((self.capacity,), dtype=torch.int32, device=dev)
+        self.next_state = torch.zeros((self.capacity, env.n_obs), **f)
+        self.reward = torch.zeros((self.capacity,), **f)
+        self.end = torch.zeros((self.capacity,), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)    # the zero fills, before the env's own stream writes
+
+    def __len__(self):
+        return min(self.pushed, self.capacity)
+
+    def struct(self) -> Replay:
+        r = Replay()
+        r.capacity = self.capacity
+        for name in ("state", "action", "next_state", "reward", "end"):
+            setattr(r, name, getattr(self, name).data_ptr())
+        return r
+
+    def sample(self, batch: int, seed: int = 0, draw: int = 0) -> dict:
+        """ReplayMemory.batch: `batch` distinct stored transitions (replay_indices(len(self), batch,
+        seed, draw)) gathered on the device: a dict of tensors state, action, next_state, reward,
+        end and index."""
+        import torch
+        batch = int(batch)
+        if not 1 <= batch <= len(self):
+            raise ValueError(f"batch {batch} of {len(self)} stored transitions")
+        dev = self.state.device
+        out = dict(state=torch.empty((batch, self.state.shape[1]), dtype=torch.float32, device=dev),
+                   action=torch.empty((batch,), dtype=torch.int32, device=dev),
+                   next_state=torch.empty((batch, self.state.shape[1]), dtype=torch.float32, device=dev),
+                   reward=torch.empty((batch,), dtype=torch.float32, device=dev),
+                   end=torch.empty((batch,), dtype=torch.uint8, device=dev),
+                   index=torch.empty((batch,), dtype=torch.int32, device=dev))
+        r, b = self.struct(), _batch_struct(out)
+        torch.cuda.synchronize(dev)     # torch-side writes to the rows (tests), the allocations
+        rc = self.env.lib.gm_replay_sample(self.env.ctx, C.byref(r), len(self), batch, C.c_uint64(seed),
+                                           C.c_uint64(draw), C.byref(b))
+        if rc != 0:
+            raise RuntimeError(self.env.lib.gm_last_error(self.env.ctx).decode() or f"gm_replay_sample failed ({rc})")
+        torch.cuda.synchronize(dev)     # the env's stream, before torch reads the batch
+        return out
+
+
 class DevicePolicy:
     """A VariableNetwork DQN policy bound to a BatchedGripperEnv (discrete actions)."""
 
@@ -106,13 +235,48 @@ class DevicePolicy:
         self._check(self.lib.gm_policy_act(self._p, C.c_float(eps), C.c_uint64(seed), C.c_uint64(decision)),
                     "gm_policy_act")
 
+    def set_params(self, params):
+        """New weights after a learner update (flat, init_params' order, or a state dict)."""
+        if isinstance(params, dict):
+            sizes, params = params_from_state_dict(params)
+            if sizes != self.sizes:
+                raise ValueError("state dict does not match the network sizes")
+        p = np.ascontiguousarray(as_f32(params), np.float32).ravel()
+        if p.size != self.params.size:
+            raise ValueError(f"{self.params.size} parameters expected, got {p.size}")
+        self.params = p.copy()
+        self._check(self.lib.gm_policy_set_params(self._p, self.params.ctypes.data_as(C.POINTER(C.c_float))),
+                    "gm_policy_set_params")
+
+    def push_begin(self, buf: ReplayBuffer):
+        """After act(): state and action of every env into the ring rows from buf.pushed on."""
+        r = buf.struct()
+        self._check(self.lib.gm_policy_push_begin(self._p, C.byref(r), buf.pushed), "gm_policy_push_begin")
+
+    def push_end(self, buf: ReplayBuffer, max_episode_steps: int | None = None):
+        """After the env-step, before the auto-reset: next_state, reward and end code into the rows
+        push_begin wrote; advances buf.pushed by n_envs."""
+        mx = self.env.max_episode_steps if max_episode_steps is None else max_episode_steps
+        r = buf.struct()
+        self._check(self.lib.gm_policy_push_end(self._p, C.byref(r), buf.pushed, int(mx)), "gm_policy_push_end")
+        buf.pushed += self.env.n_envs
+
     def rollout(self, eps, seed: int = 0, decision0: int = 0, max_episode_steps: int | None = None,
-                records_dev_ptr: int | None = None):
+                records_dev_ptr: int | None = None, replay: ReplayBuffer | None = None):
         """gm_policy_rollout: len(eps) rounds of act(eps[k], seed, decision0 + k) -> env step ->
         auto-reset, fused into one persistent launch (bit for bit the per-step sequence).
-        records_dev_ptr: device [len(eps) x n_envs] gm_episode_end records (or None)."""
+        records_dev_ptr: device [len(eps) x n_envs] gm_episode_end records (or None).
+        replay: gm_policy_rollout_replay -- the same launch also pushes every transition
+        (push_begin / push_end around each env-step) and advances replay.pushed."""
         e = np.ascontiguousarray(np.atleast_1d(eps), dtype=np.float32)
         mx = self.env.max_episode_steps if max_episode_steps is None else max_episode_steps
+        if replay is not None:
+            r = replay.struct()
+            self._check(self.lib.gm_policy_rollout_replay(
+                self._p, len(e), e.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint64(seed), C.c_uint64(decision0),
+                int(mx), C.c_void_p(records_dev_ptr or 0), C.byref(r), replay.pushed), "gm_policy_rollout_replay")
+            replay.pushed += len(e) * self.env.n_envs
+            return
         self._check(self.lib.gm_policy_rollout(self._p, len(e), e.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint64(seed),
                                                C.c_uint64(decision0), int(mx), C.c_void_p(records_dev_ptr or 0)),
                     "gm_policy_rollout")
@@ -124,6 +288,26 @@ class DevicePolicy:
         self._check(self.lib.gm_policy_read(self._p, acts.ctypes.data_as(C.POINTER(C.c_int32)),
                                             q.ctypes.data_as(C.POINTER(C.c_float))), "gm_policy_read")
         return acts, q
+
+    def td_target(self, batch: dict, gamma: float, target: "DevicePolicy | None" = None, double: bool = False,
+                  mask_terminal: bool = False):
+        """optimise_model's expected_state_action_values for a sampled batch (ReplayBuffer.sample's
+        dict; next_state, reward and end are read): (y, next_value) device tensors [batch].  self
+        is the online net, target (default: self) the target net; double: the action from self,
+        its value from target.  mask_terminal: no bootstrap where end == 1."""
+        import torch
+        tgt = self if target is None else target
+        n = int(batch["reward"].shape[0])
+        dev = batch["reward"].device
+        y = torch.empty((n,), dtype=torch.float32, device=dev)
+        v = torch.empty((n,), dtype=torch.float32, device=dev)
+        b = _batch_struct(batch)
+        torch.cuda.synchronize(dev)     # torch-side writes to the batch, the allocations
+        self._check(self.lib.gm_policy_td_target(tgt._p, self._p if double else None, C.byref(b), n, C.c_float(gamma),
+                                                 int(bool(mask_terminal)), C.c_void_p(y.data_ptr()),
+                                                 C.c_void_p(v.data_ptr())), "gm_policy_td_target")
+        torch.cuda.synchronize(dev)     # the env's stream, before torch reads the results
+        return y, v
 
     def close(self):
         if self._p:

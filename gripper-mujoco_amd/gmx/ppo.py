@@ -18,22 +18,10 @@ import ctypes as C
 import numpy as np
 
 from ._lib import load_library
-from .policy import as_f32, linear_init, state_dict_net
+from .policy import _M64, _mix, as_f32, linear_init, state_dict_net
 
 DEFAULT_HIDDEN = (64, 64)          # MLPActorCriticPG's default hidden_sizes
 LOG_STD_INIT = -0.5                # MLPGaussianActor
-
-_M64 = (1 << 64) - 1
-
-
-def _mix(z):
-    """gp_mix (csrc/gm_policy_net.h): splitmix64's finaliser on uint64 arrays."""
-    z = np.asarray(z, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        z = z + np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
 
 
 def _counters(seed, gids, decision, n_actions, j):

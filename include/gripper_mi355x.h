@@ -699,6 +699,76 @@ int  gm_policy_read(gm_policy* p, int32_t* actions, float* q);
  * launch (they are under GM_CHUNK_SUBSTEPS=0, which runs the per-step sequence). */
 int  gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed, uint64_t decision0,
                        int max_episode_steps, gm_episode_end* records);
+/* New weights after a learner update (Agent_DQN.optimise_model's optimiser step, or the soft
+ * target update of update_step, rl/agents/DQN.py:352-360): same layout as gm_policy_create's
+ * params; copied before the call returns.  A target network is a second gm_policy on the same
+ * context. */
+int  gm_policy_set_params(gm_policy* p, const float* params);
+
+/* ---- DQN replay memory, its draw and the TD target ----
+ * ReplayMemory (rl/agents/DQN.py:11-62): a bounded deque of Transition(state, action, next_state,
+ * reward, terminal), filled by Agent_DQN.update_step (:329-348) once per env-step
+ * (rl/Trainer.py:659-684, which always passes the real post-step observation as next_state).
+ * The memory is the caller's device arrays, a ring of `capacity` rows.  The ring position is the
+ * caller's too: every call takes row0, the number of transitions pushed before it, and env e at
+ * env-step k of the call writes row (row0 + k * n_envs + e) % capacity -- the deque with every env
+ * pushed in env order each env-step; no atomics, no dependence on dispatch.  A call that would
+ * write a row twice (n_steps * n_envs > capacity) fails with GM_E_ARG; capacity need not be a
+ * multiple of n_envs. */
+typedef struct gm_replay {
+  int64_t  capacity;    /* rows */
+  float*   state;       /* [capacity][n_obs]  observation the action was chosen from */
+  int32_t* action;      /* [capacity]         the discrete action taken */
+  float*   next_state;  /* [capacity][n_obs]  observation after the env-step, never the reset one */
+  float*   reward;      /* [capacity] */
+  uint8_t* end;         /* [capacity]  0 episode continues, 1 terminal (done), 2 truncated only */
+} gm_replay;
+/* a sampled batch: the caller's contiguous device arrays of `batch` rows */
+typedef struct gm_replay_batch {
+  float*   state;       /* [batch][n_obs] */
+  int32_t* action;      /* [batch] */
+  float*   next_state;  /* [batch][n_obs] */
+  float*   reward;      /* [batch] */
+  uint8_t* end;         /* [batch] */
+  int32_t* index;       /* [batch] the ring rows gathered */
+} gm_replay_batch;
+/* ReplayMemory.push in two halves around the env-step.  After gm_policy_act: state (the
+ * observation the action was chosen from) and action of every env. */
+int  gm_policy_push_begin(gm_policy* p, const gm_replay* replay, int64_t row0);
+/* After gm_step and BEFORE the auto-reset: next_state (the post-step observation), reward and
+ * end (gm_ac_record's rule: 1 done, else 2 when max_episode_steps > 0 and the episode reached
+ * it, else 0), into the rows gm_policy_push_begin(row0) wrote. */
+int  gm_policy_push_end(gm_policy* p, const gm_replay* replay, int64_t row0, int max_episode_steps);
+/* The fused form: gm_policy_rollout that also records.  For k = 0 .. n_steps - 1
+ *   gm_policy_act(eps[k], seed, decision0 + k) -> gm_policy_push_begin(row0 + k * n_envs)
+ *   -> gm_step -> gm_policy_push_end(row0 + k * n_envs, max_episode_steps)
+ *   -> gm_autoreset_episodes(max_episode_steps, spawn = NULL, records + k * n_envs)
+ * as ONE persistent launch; every array of the memory equals the per-step sequence's bit for
+ * bit, and state, observations and records equal gm_policy_rollout's with the same arguments.
+ * Under GM_CHUNK_SUBSTEPS=0 it runs that sequence.  The caller advances its count of pushed
+ * transitions by n_steps * n_envs. */
+int  gm_policy_rollout_replay(gm_policy* p, int n_steps, const float* eps, uint64_t seed, uint64_t decision0,
+                              int max_episode_steps, gm_episode_end* records, const gm_replay* replay,
+                              int64_t row0);
+/* ReplayMemory.batch (DQN.py:31-46: random.Random.sample, without replacement) as a counter-based draw:
+ * out[i], i < batch, is the image of i under a keyed bijection of [0, size), size = min(pushed,
+ * capacity) -- a balanced Feistel network of 4 rounds over the smallest even bit count b with
+ * 2^b >= size, round function splitmix64's finaliser of (key + round constant + R) masked to
+ * b / 2 bits, key from (seed, draw), cycle-walked until the value is < size.  The rows are
+ * distinct; the stream is not the agent's random.Random.  Host only, no GPU needed;
+ * batch > size is GM_E_ARG (the reference skips optimisation then, DQN.py:258). */
+int  gm_replay_indices(int64_t size, int batch, uint64_t seed, uint64_t draw, int32_t* out);
+/* The same indices computed on the device and the rows gathered into out's arrays: one kernel. */
+int  gm_replay_sample(gm_ctx* ctx, const gm_replay* replay, int64_t size, int batch, uint64_t seed,
+                      uint64_t draw, const gm_replay_batch* out);
+/* The TD target of the first n rows of a batch (Agent_DQN.optimise_model, DQN.py:294-315):
+ * y = reward + gamma * v, v the maximum of target's softmax outputs on next_state or, with
+ * online != NULL (use_double_dqn), target's output at online's first argmax.  mask_terminal = 0
+ * is the reference as written (every row bootstraps: its non_final_mask is all true);
+ * mask_terminal = 1 sets v = 0 where end == 1 and keeps the bootstrap where end == 2.
+ * Reads batch->next_state, reward and end; y, next_value (v; may be NULL): device [n]. */
+int  gm_policy_td_target(gm_policy* target, gm_policy* online, const gm_replay_batch* batch, int n, float gamma,
+                         int mask_terminal, float* y, float* next_value);
 
 /* ---- on-device PPO actor-critic, trajectory buffer and GAE ----
  * MLPActorCriticPG.step (rl/agents/PolicyGradient.py:522-528) and Agent_PPO.select_action

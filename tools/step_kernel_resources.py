@@ -24,8 +24,8 @@ import tempfile
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 SECTIONS = (".text", ".rodata", ".note")
-FUNCS = ("ac_rollout_driver", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel", "gm_policy_kernel",
-         "substep_loop", "reset_env", "driver_actions")
+FUNCS = ("ac_rollout_driver", "replay_record", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel", "gm_policy_kernel",
+         "gm_td_target_kernel", "gm_replay_sample_kernel", "substep_loop", "reset_env", "driver_actions")
 
 
 def tool(name, *args):
