@@ -4,6 +4,7 @@
 // cdof, cinert / Ic, cfrc, chain_f, chain_I, Hf, Hp, Ho, Hbb, frc (and lock_rows' lrow_*, nl).
 #pragma once
 #include "gm_real.h"
+#include "gm_rows.h"
 
 // ============================================================ kinematics
 // mj_kinematics restated (oracle.c fk): phase A, one lane per body, the hinge joint
@@ -211,9 +212,6 @@ __device__ __forceinline__ void chain_sums(SharedT<CL>& S, int b0, real* fs, rea
   }
 }
 
-// (declared, not moved here: its body needs gm_newton.hip's row helpers, which follow this stage)
-template <int CL, bool CAL>
-__device__ __forceinline__ void lock_rows(SharedT<CL>& S, const gm_model* __restrict__ m, const GmTopo* __restrict__ T, int lane);
 template <int CL, bool CAL>
 __device__ __forceinline__ void crb_rne(SharedT<CL>& S, const gm_model* __restrict__ m, const GmTopo* __restrict__ T, int lane,
                         bool prof = false) {

@@ -1,8 +1,8 @@
-// gm_integrate.h -- physics stage 4, mj_Euler: implicit joint damping (gm_newton.hip's
+// gm_integrate.h -- physics stage 4, mj_Euler: implicit joint damping (gm_euler.h's
 // euler_solve / euler_damping), the free object's quaternion step, and the calibration unit's
 // mj_checkAcc.  SharedT: reads qacc, xs; writes s.qvel, s.qpos, s.time (s.badqacc).
 #pragma once
-#include "gm_newton.hip"
+#include "gm_euler.h"
 
 GM_PHYSICS_BEGIN
 // DUO workgroups: the helper wave's euler_factor results, lane-major ([j][64]: L[1..CL], lb,

@@ -1941,7 +1941,7 @@ static void ldl6_solve(double A[6][6], double* b) {
 /* MuJoCo 2.1.5 mj_Euler's implicit joint damping (mujoco_actuators): qacc_e =
  * (M + h D)^-1 (qfrc_smooth + qfrc_constraint) = qacc - (M + h D)^-1 (h D qacc), qacc the
  * solve's (M qacc = qfrc_smooth + qfrc_constraint at its optimum).  The system on the
- * device's lanes (gm_newton.hip euler_damping): each finger chain block leaf-first LDL^T
+ * device's lanes (gm_euler.h euler_damping): each finger chain block leaf-first LDL^T
  * on its DPP row with the base as the one border column, the palm one pivot, the base
  * pivot after the wave-summed Schur complement; the object (no damping, decoupled from the
  * gripper in M) takes no correction. */

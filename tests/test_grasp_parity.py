@@ -249,7 +249,7 @@ def test_other_segment_counts_256(gm, ol, n_seg):
 def test_capped_newton_substep_matches_oracle_256(gm, ol):
     """A Newton solve that runs out of iterations (gm_model.newton_maxit = 1) on grasp
     states: mj_Euler integrates qfrc_smooth + J^T efc of the unconverged forces, not M qacc
-    (the residual path of gm_newton.hip newton_solve / euler_damping).  Device and oracle
+    (the residual path of gm_newton.hip newton_solve / gm_euler.h euler_damping).  Device and oracle
     take one substep from the same states: qpos and qvel after it to ~1e-9 (scaled), the
     capped-solve counters bit-exact, and most contact envs really capped."""
     import indep_physics as ip

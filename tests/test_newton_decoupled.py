@@ -1,5 +1,5 @@
 """The Newton point on the contact patterns that decouple the object from the gripper
-(gm_newton.hip newton_point).
+(gm_newton_point.h newton_point).
 
 The object's ground contacts are composed across the contact lanes of the object-ground
 pair and summed in slot order; when no gripper body touches the object (any_o false) the
