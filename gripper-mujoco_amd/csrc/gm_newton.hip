@@ -112,6 +112,11 @@ __device__ __forceinline__ void newton_solve(SharedT<CL>& S, const gm_model* __r
   real jq[4], jql;
   bool obj_only;
   constraint_setup<CL, CAL, DUO>(S, m, T, lane, R, jq, jql, obj_only, prof);
+#ifndef GM_NO_DECOUPLED_POINT
+  // obj_only: every contact slot below ncon is an object-ground contact, so no slot belongs to a
+  // gripper-object or gripper-ground pair: newton_point's any_o and any_g are both false
+  const bool decoupled = __builtin_amdgcn_readfirstlane((int)obj_only) != 0;
+#endif
   PH(11);
   const int ncon = S.ncon, nl = S.nl, nv = T->nv;
   const bool clane = lane < ncon;
@@ -127,6 +132,14 @@ __device__ __forceinline__ void newton_solve(SharedT<CL>& S, const gm_model* __r
 #pragma unroll
     for (int e = 0; e < 4; e++) act[e] = clane && jq[e] < 0;
     PH(13);
+#ifndef GM_NO_DECOUPLED_POINT
+    // the first point of a solve whose contacts are all the object's with the ground
+    // (wave-uniform; the same x, gm_newton_point.h).  Counted per env beside the CU id.
+    if (it == 0 && decoupled) {
+      newton_point_decoupled<CL>(S, m, T, fresh_lane(), R, act, prof);
+      if (prof && lane == 0) S.tph[27] += 1ull << 32;
+    } else
+#endif
     newton_point<CL>(S, m, T, fresh_lane(), R, act, prof);
     if (prof) t0 = clock64();
     real jx[4], jxl;

@@ -17,6 +17,8 @@
 // shared pieces (composite_add, object_columns, gm_arrow.h's) are the ones that leave every
 // kernel's vector code as it was; the rest of the assembly and the chain factor stay in
 // newton_point's body (profiles/newton_stages_code_identity.txt has the trials).
+// newton_point_decoupled, at the end of the file, is the same point for solves whose contacts
+// are all the object's with the ground: two independent blocks factored side by side.
 
 // SharedT: reads con, cbody, pair_off / pair_cnt, cdof, Hf / Hp / Ho / Hbb, frc; writes go, xs and
 // the union's nw.QF, st, fs.
@@ -618,4 +620,232 @@ __device__ void newton_point(SharedT<CL>& S, const gm_model* __restrict__ m, con
   newton_backsolve<CL>(S, T, lane, h, hb, rhs, invd);
   PH(24);
 }
+
+#ifndef GM_NO_DECOUPLED_POINT
+// ---- the decoupled Newton point: newton_point's x, bit for bit, when every contact is the
+// object on the ground (constraint_setup's obj_only, which implies !any_o && !any_g there).
+// H is then block diagonal: the gripper's arrow matrix with the base as its only border column,
+// and the object's 6x6 block.  newton_point still strings both into one chain (CL chain
+// pivots, the LDS hand-off, 28 Schur entries, 7 border pivots; the same again in the solve);
+// here the object's block rides on the chains' own instructions.  Lanes 48 + i (i = 1..6) keep
+// the object row's entries in h[1..i] -- row 3 has no chain, so h is free there -- and its
+// base-column entry in hb0; lane 48 keeps the base row.  The chain pivot statement on
+// position p of a DPP row is newton_border_factor's statement on border row bi = p, so pivots
+// 6 .. 1 of the chains and of the border are one instruction stream (the chains' pivots
+// CL .. 7 run on rows 0..2 alone), and so are the substitutions.  Only border entry (0, 0)
+// needs a Schur sum and a forward sum; both accumulate inside the loops, in newton_schur's
+// order (per chain k = CL .. 1 from +0, then rows 0, 1, 2, the palm), without LDS.
+//
+// What is left out are operations whose one operand is an exact zero, and a zero operand can
+// still change a bit: x - (+-0) (fused: x + (-+0)) returns x for every x but x = -0, which a
+// subtracted -0 turns into +0.  (Pivots are positive, H being positive definite, so scaling a
+// zero keeps its sign; no value is NaN or infinite.)  Entry by entry:
+//  - chain and palm rows' object columns hb[1..6] start at +0, stay +0 through the pivots
+//    (+0 - (+-0) = +0) and the scaling: lb = ub = +0 on these columns.
+//  - Schur entries (i, j >= 1): every sum is +0 (it starts at +0) and the palm's product is
+//    +0 * +0, so the entry is unchanged, whatever it is.  Entries (i >= 1, 0): the sums are +0
+//    again, the palm's product is +0 * ub_palm, -0 for a negative ub_palm; that subtraction is
+//    kept (hb0 - 0.0 * Hp(1,0)).  The entry itself, -dot6(cdof, 0), is computed as before.
+//  - Koo = comp + go with comp = +0: go[k] is a sum that starts at +0 and so is never -0, and
+//    +0 + x = x for every other x.  Fobj = go - (+0) = go.
+//  - the border pivots 6 .. 1 run as they did, column 0 included (lane 48 takes its multipliers
+//    a_k, zeros with a sign, from hb0's broadcast as newton_border_factor does from bk[0]); they
+//    leave entry (0, 0) alone (its update subtracts zero * zero from a positive number), so the
+//    base pivot can follow them.
+//  - forward, rows i >= 1: the sums are +0, the palm's product +0 * y_palm is kept.  Row 0:
+//    Y = rhs - sums, then Y - a_k y_k (k = 6 .. 1), zeros that matter only to Y = -0: lane 48
+//    runs these steps on a probe q = -0, which ends -0 if every product was +0 and +0
+//    otherwise, and Y + q is then what the steps make of any Y.  The k = 0 step
+//    (y - 0.0 * y_base on every border lane) is kept.
+//  - backward, border: j = 0 (y - hb0 * x_base with lane 48's value before its own step) and
+//    j = 1 .. 5 as they were.  Chain and palm rows: y - hb0 * x_base, then six subtractions of
+//    +0 * x_obj[t]: -0 for a negative x_obj[t], so together they subtract -0 if any x_obj[t] has
+//    its sign bit set and +0 otherwise; that one subtraction is kept.  The object's back
+//    substitution therefore runs before the chains', as in newton_point.
+template <int CL>
+__device__ void newton_point_decoupled(SharedT<CL>& S, const gm_model* __restrict__ m, const GmTopo* __restrict__ T, int lane,
+                                       const RowsT& R, const bool* act, bool prof) {
+  static_assert(CL >= 7, "the object's six columns sit in h[1..6] and ride on pivots 6 .. 1");
+  unsigned long long t0 = prof ? clock64() : 0;
+  const int ncon = S.ncon, nl = S.nl;
+  real Q[6], F[3];
+  newton_contact_qf<CL>(S, lane, ncon, R, act, Q, F);
+  newton_ground_composites<CL>(S, T, lane, ncon, Q, F);
+  PH(3);
+  GM_WAVE_SYNC();   // S.go is written
+  PH(4);
+  // ---- H and rhs on the factor lanes: H~'s own entries on the gripper rows
+  real h[CL + 1], hb0 = 0, rhs = 0;
+#pragma unroll
+  for (int j = 0; j <= CL; j++) h[j] = 0;
+  const int rowf = lane >> 4, p = lane & 15;
+  const bool chainrow = rowf < 3 && p >= 1 && p <= CL;
+  const bool border = lane >= 48 && lane < 55;
+  if (chainrow) {
+    const int d = T->dof_f0[rowf] + p - 1;
+    const real* H = S.Hf[rowf];
+    real Hr[CL + 1];
+#pragma unroll
+    for (int j = 0; j <= CL; j++) Hr[j] = H[TRI(p, j)];
+    keep_n<CL + 1>(Hr);
+#pragma unroll
+    for (int j = 1; j <= CL; j++) h[j] = (j <= p) ? Hr[j] : h[j];
+    hb0 = Hr[0];
+    rhs = S.frc[d];
+  } else if (lane == GM_LANE_PALM_F) {
+    h[1] = S.Hp[TRI(1, 1)];
+    hb0 = S.Hp[TRI(1, 0)];
+    rhs = S.frc[T->dof_palm];
+  } else if (lane == 48) {
+    hb0 = S.Hbb;
+    rhs = S.frc[T->dof_base];
+  } else if (border) {
+    const int k = lane - 49;
+    const real yob[6] = {0, 0, 0, 0, 0, 0};
+    real KC[27], yk[6];   // Koo (21) then the row's cdof (6), loaded in one batch
+#pragma unroll
+    for (int t = 0; t < 21; t++) KC[t] = S.go[t];
+#pragma unroll
+    for (int t = 0; t < 6; t++) KC[21 + t] = S.cdof[T->dof_obj + k][t];
+    keep_n<27>(KC);
+    const real* cok = KC + 21;
+    symK_mul(KC, cok, yk);
+    hb0 = -dot6(cok, yob);
+    hb0 = hb0 - 0.0 * S.Hp[TRI(1, 0)];   // (the Schur step's palm product)
+    object_columns<CL>(S, T, [&](int l, const real* co) {
+      const real v = S.Ho[TRI(k, l)] + dot6(co, yk);
+      keep(v);
+      h[1 + l] = (l <= k) ? v : h[1 + l];
+    });
+    rhs = S.frc[T->dof_obj + k] + dot6(cok, S.go + 21);
+  }
+  // motor-lock rows (1-dof joint equalities): D on the diagonal, D aref on the rhs
+  for (int r = 0; r < nl; r++) {
+    const int d = __builtin_amdgcn_readlane(R.ldof, r);
+    const real lD = readlane_real(R.lD, r), lR = readlane_real(R.lD * R.laref, r);
+    if (T->dof_grp[d] < 3) {
+      const int f = T->dof_grp[d], pd = T->dof_p[d];
+      if (rowf == f && p == pd) {
+#pragma unroll
+        for (int j = 1; j <= CL; j++) if (j == pd) h[j] += lD;
+        rhs += lR;
+      }
+    } else if (lane == GM_LANE_PALM_F) {
+      h[1] += lD;
+      rhs += lR;
+    }
+  }
+  PH(7);
+  // ---- factor.  The palm's pivot first (wave-uniform copies: ub, lb, y); the base sum
+  // sacc = sum lb ub of the lane's own chain accumulates beside the pivots
+  real invd = 1.0, sacc = 0.0;
+  const real pub = readlane_real(hb0, GM_LANE_PALM_F), ypalm = readlane_real(rhs, GM_LANE_PALM_F);
+  const real pih = rcp_piv(readlane_real(h[1], GM_LANE_PALM_F));
+  const real plb = pub * pih;
+  // one pivot of the chain factor (newton_point's statements with a one-wide border); ROW3:
+  // the border rows ride (newton_border_factor's statements: bi = p, column 0 in hb0)
+#define GM_DEC_PIVOT(ROW3) do { \
+    const real hkk = row_bcast(h[k], k); \
+    const real ihk = rcp_piv(hkk); \
+    real hk[CL + 1]; \
+    _Pragma("unroll") for (int j = 1; j < k; j++) hk[j] = row_bcast(h[j], k); \
+    const real hkb = row_bcast(hb0, k); \
+    const bool upd = ((ROW3) && rowf == 3) ? p < k : (p >= 1 && p < k); \
+    const bool piv = p == k; \
+    real Hpk = ((ROW3) && lane == 48) ? hkb : 0.0; \
+    _Pragma("unroll") for (int j = 1; j < k; j++) Hpk = (p == j) ? hk[j] : Hpk; \
+    const real a = Hpk * ihk; \
+    const real aa = upd ? a : 0.0; \
+    const real lbk = hkb * ihk; \
+    sacc = sacc + lbk * hkb; \
+    _Pragma("unroll") for (int j = 1; j < k; j++) h[j] = h[j] - hk[j] * aa; \
+    hb0 = hb0 - hkb * aa; \
+    h[k] = upd ? a : h[k]; \
+    invd = piv ? ihk : invd; \
+  } while (0)
+  if (lane < 48) {
+#pragma unroll
+    for (int k = CL; k >= 7; k--) GM_DEC_PIVOT(false);
+  }
+  if (lane < 55) {
+#pragma unroll
+    for (int k = 6; k >= 1; k--) GM_DEC_PIVOT(true);
+#pragma unroll
+    for (int j = 1; j < CL; j++) h[j] = (j < p) ? h[j] * invd : h[j];
+    hb0 = (lane == 48) ? hb0 : hb0 * invd;
+  } else if (lane == GM_LANE_PALM_F) {
+    hb0 = hb0 * pih;
+    invd = pih;
+  }
+#undef GM_DEC_PIVOT
+  // border entry (0, 0): newton_schur's sums, then the base pivot
+  const real sa0 = readlane_real(sacc, 1), sa1 = readlane_real(sacc, 17), sa2 = readlane_real(sacc, 33);
+  if (lane == 48) {
+    hb0 = (((hb0 - sa0) - sa1) - sa2) - plb * pub;
+    invd = rcp_piv(hb0);
+  }
+  PH(14);
+  // ---- solve: forward (the base row's sum facc = sum lb y beside the steps; lane 48 runs
+  // the probe), the base row, D, backward
+  real y = rhs, facc = 0.0;
+  if (border) y = (lane == 48) ? -0.0 : y - 0.0 * ypalm;
+#define GM_DEC_FORWARD(ROW3) do { \
+    const real yk = row_bcast(y, k); \
+    const real lbk = row_bcast(hb0, k); \
+    facc = facc + lbk * yk; \
+    const bool upd = ((ROW3) && rowf == 3) ? p < k : (p >= 1 && p < k); \
+    const real Lc = upd ? h[k] : 0.0; \
+    y = y - Lc * yk; \
+  } while (0)
+  if (lane < 48) {
+#pragma unroll
+    for (int k = CL; k >= 7; k--) GM_DEC_FORWARD(false);
+  }
+  if (lane < 55) {
+#pragma unroll
+    for (int k = 6; k >= 1; k--) GM_DEC_FORWARD(true);
+  }
+#undef GM_DEC_FORWARD
+  const real fa0 = readlane_real(facc, 1), fa1 = readlane_real(facc, 17), fa2 = readlane_real(facc, 33);
+  if (lane == 48) {
+    const real Y = (((rhs - fa0) - fa1) - fa2) - plb * ypalm;
+    y = Y + y;
+  }
+  const real yb6 = readlane_real(y, 48);
+  if (border) y = y - 0.0 * yb6;
+  y = y * invd;
+  const real tb = readlane_real(y, 48);
+  if (border) {
+    const real Lr0 = (lane > 48) ? hb0 : 0.0;
+    y = y - Lr0 * tb;
+#pragma unroll
+    for (int j = 1; j < 6; j++) {
+      const real xj = row_bcast(y, j);
+      const real Lr = (j < p) ? h[j] : 0.0;
+      y = y - Lr * xj;
+    }
+  }
+  real xb[7];
+#pragma unroll
+  for (int t = 0; t < 7; t++) xb[t] = readlane_real(y, 48 + t);
+  bool neg = false;
+#pragma unroll
+  for (int t = 1; t < 7; t++) neg = neg || __double_as_longlong(xb[t]) < 0;
+  const real zsub = neg ? -0.0 : 0.0;
+  if (lane < 48) {
+    y = y - hb0 * xb[0];
+    y = y - zsub;
+    y = chain_backward<CL>(y, h, p);
+    if (chainrow) S.xs[T->dof_f0[rowf] + p - 1] = y;
+  } else if (lane == GM_LANE_PALM_F) {
+    y = y - hb0 * xb[0];
+    y = y - zsub;
+    S.xs[T->dof_palm] = y;
+  } else if (border) {
+    S.xs[lane == 48 ? T->dof_base : T->dof_obj + lane - 49] = y;
+  }
+  GM_WAVE_SYNC();
+  PH(24);
+}
+#endif
 GM_PHYSICS_END

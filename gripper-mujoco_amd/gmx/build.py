@@ -16,6 +16,28 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-mllvm", "-disable-machine-licm"]
 
 
+# the same sources with the decoupled Newton point compiled out (csrc/gm_newton.hip): the
+# library tests/test_decoupled_point.py compares the default one with, byte for byte
+NO_DECOUPLED_LIB = os.path.join(os.path.dirname(LIB_PATH), "libgm_no_decoupled.so")
+
+
+def _deps():
+    csrc = os.path.join(PKG_DIR, "csrc")
+    return sorted(os.path.join(PKG_DIR, s) for s in SOURCES) + \
+        sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".inc"))) + \
+        [os.path.join(REPO_DIR, "include", f) for f in ("gripper_mi355x.h", "gm_settings.def")]
+
+
+def build_no_decoupled(verbose: bool = False) -> str:
+    """build(out=NO_DECOUPLED_LIB, extra_flags=["-DGM_NO_DECOUPLED_POINT"]), unless that
+    library is already newer than every source."""
+    if os.path.exists(NO_DECOUPLED_LIB):
+        t = os.path.getmtime(NO_DECOUPLED_LIB)
+        if all(os.path.getmtime(d) <= t for d in _deps()):
+            return NO_DECOUPLED_LIB
+    return build(verbose=verbose, out=NO_DECOUPLED_LIB, extra_flags=["-DGM_NO_DECOUPLED_POINT"])
+
+
 def build(verbose: bool = False, force: bool = False, out: str | None = None, extra_flags=()) -> str:
     """Compile each translation unit in parallel (the env-step kernel and the calibration
     variant are separate device modules), then link libgm.so (or `out`: developer A/B

@@ -444,4 +444,8 @@ class BatchedGripperEnv:
         """One env-step with per-phase shader-clock counters (lane 0, summed over substeps)."""
         ph = np.zeros((self.n_envs, self.N_PHASE), dtype=np.uint64)
         self._check(self.lib.gm_step_profiled(self._ctx, ph.ctypes.data_as(C.POINTER(C.c_uint64))))
+        # the "cu" column carries a second counter in its upper half: the solves of this
+        # env-step whose first Newton point took the decoupled path (newton_point_decoupled)
+        self.decoupled_points = (ph[:, 27] >> np.uint64(32)).astype(np.int64)
+        ph[:, 27] &= np.uint64(0xFFFFFFFF)
         return ph

@@ -35,9 +35,17 @@ for t in range(MAX_EP):
         env.lib.gm_reset(env.ctx, np.ascontiguousarray(m.astype(np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), None)
     drive()
 tot = np.zeros(env.N_PHASE)
+dropped = 0
 for t in range(3):
-    tot += drive(True).astype(np.float64).mean(axis=0)
+    ph = drive(True).astype(np.float64)
+    # a clock difference that wrapped (a phase's two clock reads out of order) is ~2^64: one
+    # such env would swamp the mean of 4096, so its row is left out and counted
+    ok = (ph[:, :25] < 2.0 ** 48).all(axis=1)
+    dropped += int((~ok).sum())
+    tot += ph[ok].mean(axis=0)
 tot /= 3
+if dropped:
+    print(f"({dropped} env rows with a wrapped clock difference left out of the means)")
 S = 63
 TOP = [0, 1, 2, 5, 6, 8, 9, 10]
 allc = tot[TOP].sum()

@@ -1,4 +1,4 @@
-"""SQ counters of the headline's rollout launches from tools/pmc_r06.sh (passes sq1, sq2):
+"""SQ counters of the headline's rollout launches from tools/pmc_sq_rollout.sh (passes sq1, sq2):
 the step kernel's dispatches over 5x the per-step launches' median duration are the
 gm_rollout launches (R env-steps of every env); counters per launch, per env-substep
 (R x n_envs x S) and as wave-cycle fractions, the VALU lane utilisation.
@@ -47,7 +47,7 @@ def main(d, R, n, out=None):
         res["valu_lane_utilisation"] = round(acc["SQ_THREAD_CYCLES_VALU"] / (64 * acc["SQ_ACTIVE_INST_VALU"]), 4)
     if "SQ_LDS_BANK_CONFLICT" in acc and "SQ_ACTIVE_INST_LDS" in acc:
         res["lds_bank_conflict_fraction_of_lds_active"] = round(acc["SQ_LDS_BANK_CONFLICT"] / acc["SQ_ACTIVE_INST_LDS"], 4)
-    res["source"] = (f"tools/pmc_r06.sh: rocprofv3 --pmc SQ passes (sq1, sq2; each its own run) over bench.py "
+    res["source"] = (f"tools/pmc_sq_rollout.sh: rocprofv3 --pmc SQ passes (sq1, sq2; each its own run) over bench.py "
                      f"--steps 10 --warmup 10 (headline only), the {R}-env-step gm_rollout launches of the C3 benchmark mix")
     s = json.dumps(res, indent=1)
     print(s)
