@@ -24,7 +24,8 @@ __device__ __noinline__ real impedance_pow(real x, real mid, real pw) {
 __device__ __forceinline__ real impedance(const gm_model* __restrict__ m, real r) {
   const real dmin = m->solimp[0], dmax = m->solimp[1], width = m->solimp[2];
   const real mid = m->solimp[3], pw = m->solimp[4];
-  if (dmin == dmax || width <= 1e-15) return dmin;
+  // a flat sigmoid (MuJoCo getimpedance: equal ends or a width under mjMINVAL): the mean of the ends
+  if (dmin == dmax || width <= 1e-15) return 0.5 * (dmin + dmax);
   const real x = div_n(fabs(r), width);
   real y;
   if (pw == 2) {   // MuJoCo's default power

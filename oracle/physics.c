@@ -1091,7 +1091,7 @@ static void collision(or_env* e) {
  * ===================================================================== */
 static double impedance(const gm_model* m, double r) {
   const double dmin = m->solimp[0], dmax = m->solimp[1], width = m->solimp[2], mid = m->solimp[3], pw = m->solimp[4];
-  if (dmin == dmax || width <= 1e-15) return dmin;
+  if (dmin == dmax || width <= 1e-15) return 0.5 * (dmin + dmax);   /* flat: the mean of the ends, as getimpedance */
   const double x = fabs(r) / width;
   if (x >= 1) return dmax;
   if (x <= 0) return dmin;

@@ -34,7 +34,7 @@ import oracle_lib as ol
 PLANE, SPH, CYL, BOX = ip.GEOM_PLANE, ip.GEOM_SPHERE, ip.GEOM_CYLINDER, ip.GEOM_BOX
 CLOSED, ORACLE = "closed", "oracle"
 MPR_DEPTH, MPR_NORMAL = 1e-6, 2e-3          # the convex collider's own tolerance (test_mpr_cylinder_box)
-TIMESTEP = {8: None, 10: 2.1e-3}            # N = 10 at the step test_ten_segment_fingers_256 uses
+TIMESTEP = {8: None, 10: 2.1e-3, 5: 6.76e-3}  # N = 10 / 5 at the steps test_grasp_parity.py uses for them
 FAR = np.array([0.3, 0.3])                  # object placed here touches nothing but the ground
 Z = np.array([0.0, 0.0, 1.0])
 TILT = 1e-4                                 # takes flush box faces off the exact-parallel tie (box_cases)
