@@ -22,6 +22,7 @@
 #include "gm_env_kernels.hip"
 #include "gm_policy.hip"
 #include "gm_replay.hip"
+#include "gm_learn.hip"
 #include "gm_ac.hip"
 
 // calibration translation unit (gm_calib.hip)
@@ -1557,6 +1558,280 @@ int gm_policy_read(gm_policy* p, int32_t* actions, float* q) {
     HIPCHK(c, hipMemcpyAsync(q, p->d_q, sizeof(float) * (size_t)c->n_envs * c->cfg.n_actions,
                              hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- on-device DQN learner
+struct gm_learner {
+  gm_ctx* ctx = nullptr;
+  gm_policy* online = nullptr;
+  gm_dqn_opt opt{};
+  GlPlan plan{};
+  int64_t step = 0;             // optimiser steps taken
+  int64_t flat = 0;             // parameters in gm_policy_create's flat order
+  DevBuf<float> d_partials;     // [GL_MAX_TILES][total] per-tile gradients
+  DevBuf<float> d_tile_loss;    // [GL_MAX_TILES]
+  DevBuf<float> d_grad, d_m, d_v, d_vmax;   // [total], packed order
+  DevBuf<float> d_loss;         // [1] mean loss of the held gradient
+  DevBuf<float> d_spill;        // the gradient kernel's rows where they do not fit LDS
+  // gm_learner_train's batch and TD target
+  DevBuf<float> d_state, d_next, d_reward, d_y;
+  DevBuf<int32_t> d_action, d_index;
+  DevBuf<uint8_t> d_end;
+};
+
+// the optimiser's launch arguments for step t (>= 1): torch's scalars, each formed in double
+static GlOpt learner_opt(const gm_dqn_opt& o, int64_t t) {
+  GlOpt g{};
+  g.optimiser = o.optimiser;
+  g.amsgrad = o.amsgrad;
+  g.omb1 = (float)(1.0 - o.beta1);
+  g.beta2 = (float)o.beta2;
+  g.omb2 = (float)(1.0 - o.beta2);
+  g.eps = (float)o.eps;
+  g.wd = (float)o.weight_decay;
+  g.decay = (float)(1.0 - o.lr * o.weight_decay);
+  g.clamp = (float)o.grad_clamp;
+  g.step_size = (float)(o.lr / (1.0 - std::pow(o.beta1, (double)t)));
+  g.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(o.beta2, (double)t));
+  return g;
+}
+// one launch of gm_learn_step_kernel over the online net's packed elements
+static hipError_t learner_launch_step(gm_learner* l, bool sum, bool step, gm_policy* target, float tau, int n,
+                                      float* loss_out) {
+  gm_ctx* c = l->ctx;
+  GlStepArgs a{};
+  a.do_sum = sum;
+  a.do_step = step;
+  a.do_soft = target != nullptr;
+  a.n_tiles = (n + GP_TILE - 1) / GP_TILE;
+  a.n = n;
+  a.total = (long long)l->online->total;
+  a.partials = l->d_partials;
+  a.tile_loss = l->d_tile_loss;
+  a.grad = l->d_grad;
+  a.loss = l->d_loss;
+  a.loss_out = loss_out;
+  a.p = l->online->d_params;
+  a.m = l->d_m;
+  a.v = l->d_v;
+  a.vmax = l->d_vmax;
+  a.target = target ? target->d_params.get() : nullptr;
+  a.tau = tau;
+  a.opt = learner_opt(l->opt, std::max<int64_t>(l->step, 1));
+  const int threads = 256;
+  hipLaunchKernelGGL(gm_learn_step_kernel, dim3((unsigned)((a.total + threads - 1) / threads)), dim3(threads), 0,
+                     c->stream, a);
+  return hipGetLastError();
+}
+static hipError_t learner_launch_grad(gm_learner* l, const float* state, const int32_t* action, const float* y, int n) {
+  gm_policy* p = l->online;
+  hipLaunchKernelGGL(gm_learn_grad_kernel, dim3((n + GP_TILE - 1) / GP_TILE), dim3(64), 0, l->ctx->stream, state,
+                     action, y, n, p->d_params, p->net, l->plan, (int)l->opt.loss, l->d_spill, l->d_partials,
+                     (long long)p->total, l->d_tile_loss);
+  return hipGetLastError();
+}
+// packed device array -> flat host array (out) through one copy
+static int learner_unpack(gm_ctx* c, const GpNet& P, int64_t total, const float* d_packed, float* out) {
+  std::vector<float> packed((size_t)total);
+  const int rc = read_back(c, packed.data(), d_packed, sizeof(float) * (size_t)total);
+  if (rc != GM_OK) return rc;
+  gl_for_each_param(P, [&](int64_t i, int64_t k) { out[i] = packed[(size_t)k]; });
+  return GM_OK;
+}
+static bool same_sizes(const gm_policy* a, const gm_policy* b) { return a->sizes == b->sizes && a->total == b->total; }
+
+extern "C" {
+
+void gm_dqn_opt_default(gm_dqn_opt* out) {
+  if (!out) return;
+  *out = gm_dqn_opt{GM_OPT_ADAMW, 1, GM_LOSS_SMOOTH_L1, 0, 1e-4, 0.9, 0.999, 1e-8, 0.01, 100.0};
+}
+
+int gm_learner_create(gm_policy* online, const gm_dqn_opt* opt, gm_learner** out) {
+  if (!online || !online->ctx || !out) return GM_E_ARG;
+  gm_ctx* c = online->ctx;
+  gm_dqn_opt o;
+  gm_dqn_opt_default(&o);
+  if (opt) o = *opt;
+  if ((o.optimiser != GM_OPT_ADAM && o.optimiser != GM_OPT_ADAMW) || (o.loss != GM_LOSS_SMOOTH_L1 && o.loss != GM_LOSS_MSE))
+    return fail(c, GM_E_ARG, "gm_learner_create: optimiser must be GM_OPT_ADAM / GM_OPT_ADAMW, loss GM_LOSS_SMOOTH_L1 / GM_LOSS_MSE");
+  if (!(o.lr >= 0) || !(o.beta1 >= 0 && o.beta1 < 1) || !(o.beta2 >= 0 && o.beta2 < 1) || !(o.eps >= 0) || !(o.weight_decay >= 0))
+    return fail(c, GM_E_ARG, "gm_learner_create: lr, eps, weight_decay >= 0 and betas in [0, 1) expected");
+  HIPCHK(c, hipSetDevice(c->device));
+  gm_learner* l = new gm_learner;
+  l->ctx = c;
+  l->online = online;
+  l->opt = o;
+  l->plan = gl_plan(online->net);
+  l->flat = gl_flat_count(online->net);
+  const size_t total = (size_t)online->total, n_obs = (size_t)c->cfg.n_obs;
+  hipError_t e = l->d_partials.alloc(total * GL_MAX_TILES);
+  if (e == hipSuccess) e = l->d_tile_loss.alloc(GL_MAX_TILES);
+  if (e == hipSuccess) e = l->d_grad.alloc(total);
+  if (e == hipSuccess) e = l->d_m.alloc(total);
+  if (e == hipSuccess) e = l->d_v.alloc(total);
+  if (e == hipSuccess) e = l->d_vmax.alloc(total);
+  if (e == hipSuccess) e = l->d_loss.alloc(1);
+  if (e == hipSuccess) e = l->d_spill.alloc(l->plan.total > GL_ARENA ? (size_t)l->plan.total * GL_MAX_TILES : 1);
+  if (e == hipSuccess) e = l->d_state.alloc(n_obs * GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_next.alloc(n_obs * GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_reward.alloc(GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_y.alloc(GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_action.alloc(GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_index.alloc(GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_end.alloc(GL_MAX_BATCH);
+  for (float* z : {l->d_grad.get(), l->d_m.get(), l->d_v.get(), l->d_vmax.get()})
+    if (e == hipSuccess) e = hipMemsetAsync(z, 0, sizeof(float) * total, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(l->d_loss, 0, sizeof(float), c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    gm_learner_destroy(l);
+    return fail(c, GM_E_HIP, std::string("gm_learner_create: ") + hipGetErrorString(e));
+  }
+  *out = l;
+  return GM_OK;
+}
+
+void gm_learner_destroy(gm_learner* l) {
+  if (!l) return;
+  if (l->ctx) {
+    (void)hipSetDevice(l->ctx->device);
+    (void)hipStreamSynchronize(l->ctx->stream);   // the stream may still use the learner's buffers
+  }
+  delete l;
+}
+
+int gm_learner_grad(gm_learner* l, const gm_replay_batch* batch, const float* y, int n) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  if (!batch || !batch->state || !batch->action || !y || n < 1)
+    return fail(c, GM_E_ARG, "gm_learner_grad: incomplete batch (state, action), no y or n < 1");
+  if (n > GL_MAX_BATCH)
+    return fail(c, GM_E_ARG, "gm_learner_grad: " + std::to_string(n) + " rows, the learner holds " +
+                                 std::to_string(GL_MAX_BATCH));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, learner_launch_grad(l, batch->state, batch->action, y, n));
+  HIPCHK(c, learner_launch_step(l, true, false, nullptr, 0.0f, n, nullptr));
+  return GM_OK;
+}
+
+int gm_learner_step(gm_learner* l) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  l->step++;
+  HIPCHK(c, learner_launch_step(l, false, true, nullptr, 0.0f, 1, nullptr));
+  return GM_OK;
+}
+
+int gm_learner_read(gm_learner* l, float* grad_flat, float* loss) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (grad_flat) {
+    const int rc = learner_unpack(c, l->online->net, l->online->total, l->d_grad, grad_flat);
+    if (rc != GM_OK) return rc;
+  }
+  return loss ? read_back(c, loss, l->d_loss, sizeof(float)) : (int)GM_OK;
+}
+
+int gm_learner_get_state(gm_learner* l, int64_t* step, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (step) *step = l->step;
+  const float* src[3] = {l->d_m, l->d_v, l->d_vmax};
+  float* dst[3] = {exp_avg, exp_avg_sq, max_exp_avg_sq};
+  for (int i = 0; i < 3; i++)
+    if (dst[i]) {
+      const int rc = learner_unpack(c, l->online->net, l->online->total, src[i], dst[i]);
+      if (rc != GM_OK) return rc;
+    }
+  return GM_OK;
+}
+
+int gm_learner_set_state(gm_learner* l, const int64_t* step, const float* exp_avg, const float* exp_avg_sq,
+                         const float* max_exp_avg_sq) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  if (step && *step < 0) return fail(c, GM_E_ARG, "gm_learner_set_state: negative step");
+  HIPCHK(c, hipSetDevice(c->device));
+  const float* src[3] = {exp_avg, exp_avg_sq, max_exp_avg_sq};
+  float* dst[3] = {l->d_m, l->d_v, l->d_vmax};
+  gm_policy* p = l->online;
+  std::vector<float> packed((size_t)p->total);
+  for (int i = 0; i < 3; i++)
+    if (src[i]) {
+      gm_policy_pack(p->sizes.data(), (int)p->sizes.size(), src[i], packed.data());
+      const int rc = stage_upload(c, dst[i], packed.data(), sizeof(float) * (size_t)p->total);
+      if (rc != GM_OK) return rc;
+    }
+  if (step) l->step = *step;
+  return GM_OK;
+}
+
+int gm_policy_get_params(gm_policy* p, float* flat) {
+  if (!p || !p->ctx || !flat) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  return learner_unpack(c, p->net, p->total, p->d_params, flat);
+}
+
+int gm_policy_get_packed(gm_policy* p, float* packed) {
+  if (!p || !p->ctx || !packed) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  return read_back(c, packed, p->d_params, sizeof(float) * (size_t)p->total);
+}
+
+int gm_policy_soft_update(gm_policy* target, gm_policy* online, float tau) {
+  if (!target || !target->ctx || !online) return GM_E_ARG;
+  gm_ctx* c = target->ctx;
+  if (online->ctx != c) return fail(c, GM_E_ARG, "gm_policy_soft_update: the two policies belong to different contexts");
+  if (!same_sizes(target, online)) return fail(c, GM_E_ARG, "gm_policy_soft_update: the two policies differ in their layer sizes");
+  if (!(tau >= 0.0f && tau <= 1.0f)) return fail(c, GM_E_ARG, "gm_policy_soft_update: tau in [0, 1] expected");
+  HIPCHK(c, hipSetDevice(c->device));
+  GlStepArgs a{};
+  a.do_soft = 1;
+  a.total = (long long)online->total;
+  a.p = online->d_params;
+  a.target = target->d_params;
+  a.tau = tau;
+  const int threads = 256;
+  hipLaunchKernelGGL(gm_learn_step_kernel, dim3((unsigned)((a.total + threads - 1) / threads)), dim3(threads), 0,
+                     c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return GM_OK;
+}
+
+int gm_learner_train(gm_learner* l, gm_policy* target, const gm_replay* replay, int64_t size, int batch, uint64_t seed,
+                     uint64_t draw0, int n_updates, float gamma, int double_dqn, int mask_terminal, float tau,
+                     float* losses) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  gm_policy* online = l->online;
+  if (target && target->ctx != c) return fail(c, GM_E_ARG, "gm_learner_train: the two policies belong to different contexts");
+  if (target && !same_sizes(target, online)) return fail(c, GM_E_ARG, "gm_learner_train: the two policies differ in their layer sizes");
+  if (n_updates < 1) return fail(c, GM_E_ARG, "gm_learner_train: n_updates < 1");
+  if (batch > GL_MAX_BATCH)
+    return fail(c, GM_E_ARG, "gm_learner_train: batch " + std::to_string(batch) + ", the learner holds " +
+                                 std::to_string(GL_MAX_BATCH));
+  if (tau > 0.0f && (!target || target == online || !(tau <= 1.0f)))
+    return fail(c, GM_E_ARG, "gm_learner_train: a soft update needs a target policy of its own and tau <= 1");
+  const bool soft = tau > 0.0f;
+  gm_policy* tdnet = target ? target : online;
+  const gm_replay_batch b{l->d_state, l->d_action, l->d_next, l->d_reward, l->d_end, l->d_index};
+  for (int u = 0; u < n_updates; u++) {
+    int rc = gm_replay_sample(c, replay, size, batch, seed, draw0 + (uint64_t)u, &b);   // (validates replay, size, batch)
+    if (rc == GM_OK) rc = gm_policy_td_target(tdnet, double_dqn ? online : nullptr, &b, batch, gamma, mask_terminal, l->d_y, nullptr);
+    if (rc != GM_OK) return rc;
+    HIPCHK(c, learner_launch_grad(l, l->d_state, l->d_action, l->d_y, batch));
+    l->step++;
+    HIPCHK(c, learner_launch_step(l, true, true, soft ? target : nullptr, tau, batch, losses ? losses + u : nullptr));
+  }
   return GM_OK;
 }
 

@@ -612,6 +612,7 @@ int64_t gm_struct_size(int which) {
     case 5: return (int64_t)sizeof(gm_model_params);
     case 6: return (int64_t)sizeof(gm_spawn_params);
     case 7: return (int64_t)sizeof(gm_calibration);
+    case 8: return (int64_t)sizeof(gm_dqn_opt);
     default: return -1;
   }
 }

@@ -1,0 +1,229 @@
+// gm_learn.hip -- the DQN learner's kernels: the loss gradient of a batch (gm_learn_grad_kernel,
+// one wave per 16 rows, partial sums per tile) and the elementwise kernel that sums the tiles in
+// order, steps Adam / AdamW and soft-updates a target net (gm_learn_step_kernel).  Shared rules
+// and the row plan are gm_learn.h's; the forward is gm_policy_net.h's chain, kept layer by layer.
+//
+// Kernels are ordered by the context's stream and, inside a kernel, by workgroup barriers only:
+// no workgroup waits for another one, and no float atomic is used, so two runs give the same bits.
+#pragma once
+#include "gm_learn.h"
+
+// The gradient of mean_i loss(softmax(net(state_i))[action_i] - y_i) over n rows with respect to
+// the packed weights: this tile's 16 rows' share into partials[tile][total] (every entry written,
+// padding entries with 0) and the tile's loss sum into tile_loss[tile].
+//
+// Forward: gp_forward_tile's arithmetic (same MFMA chain, k order, bias placement), every layer's
+// post-activation rows kept -- in LDS when the plan fits GL_ARENA, else in this tile's part of
+// `spill` (global, owned by the learner; written and read by this wave only, between barriers).
+// Backward, per layer l from the last: with D the deltas dL/dz of layer l's outputs (0 in padded
+// columns and in rows >= n) and A the layer's input rows,
+//   dW[j][k] = sum_i D[i][j] A[i][k]   MFMA with M = 16 k's of four k steps, N = 16 j's of a tile,
+//                                       reduction over the batch rows in four chunks of 4; row m
+//                                       of the product stands for k = 4 (s0 + (m & 3)) + (m >> 2),
+//                                       so register r of lane (g, n) is packed element
+//                                       (tile t, k step s0 + r, lane 16 g + n): coalesced stores;
+//   db[j]    = sum_i D[i][j]            in row order;
+//   Dprev[i][k] = [A[i][k] > 0] sum_j D[i][j] W[j][k]   MFMA with M = the 16 rows, N = 16 k's,
+//                                       reduction over j in steps of 4, W gathered from the
+//                                       B-fragment order (4 consecutive floats per (k, j quad)).
+__global__ __launch_bounds__(64) void gm_learn_grad_kernel(const float* __restrict__ state,
+                                                           const int32_t* __restrict__ action,
+                                                           const float* __restrict__ y, int n,
+                                                           const float* __restrict__ params, GpNet P, GlPlan L,
+                                                           int loss_kind, float* __restrict__ spill,
+                                                           float* __restrict__ partials, long long total,
+                                                           float* __restrict__ tile_loss) {
+  __shared__ float arena[GL_ARENA];
+  __shared__ float row_loss[GP_TILE];
+  const int lane = threadIdx.x;
+  const int g = lane >> 4, nn = lane & 15;
+  const int e0 = blockIdx.x * GP_TILE;
+  float* base = L.total <= GL_ARENA ? arena : spill + (size_t)blockIdx.x * L.total;
+  float* part = partials + (size_t)blockIdx.x * total;
+
+  // ---- forward, every layer's rows kept
+  {
+    const int n_obs = P.width[0], k0 = P.kpad[0], S0 = L.a_stride[0];
+    float* A0 = base + L.a_off[0];
+    for (int i = lane; i < GP_TILE * k0; i += 64) {
+      const int r = i / k0, k = i - r * k0;
+      A0[r * S0 + k] = (e0 + r < n && k < n_obs) ? state[(size_t)(e0 + r) * n_obs + k] : 0.0f;
+    }
+  }
+  __syncthreads();
+  for (int l = 0; l < P.n_layers; l++) {
+    const float* __restrict__ W = params + P.woff[l];
+    const float* __restrict__ Bv = params + P.boff[l];
+    const int ksteps = P.kpad[l] >> 2;
+    const bool last = (l == P.n_layers - 1);
+    const int outw = P.width[l + 1];
+    const float* in = base + L.a_off[l];
+    float* out = base + L.a_off[l + 1];
+    const int Si = L.a_stride[l], So = L.a_stride[l + 1];
+    for (int t = 0; t < P.tiles[l]; t++) {
+      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+      const float* Wt = W + (size_t)t * ksteps * 64;
+      for (int s = 0; s < ksteps; s++) {
+        const float a = in[nn * Si + 4 * s + g];
+        const float b = Wt[s * 64 + lane];
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+      }
+      const int j = t * 16 + nn;
+      const float bias = Bv[j];
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        float v = c[r] + bias;
+        if (!last) v = gp_activate(v, GP_ACT_RELU);
+        out[(g * 4 + r) * So + j] = (j < outw) ? v : 0.0f;
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- loss and the deltas of the logits: one lane per row
+  const int nl = P.n_layers;
+  const int n_out = P.width[nl];
+  const int Sd = L.d_stride;
+  int cur = 0;
+  {
+    float* D = base + L.d_off[0];
+    const int wd = P.tiles[nl - 1] * 16;
+    if (lane < GP_TILE) {
+      float* drow = D + lane * Sd;
+      float ls = 0.0f;
+      if (e0 + lane < n) {
+        const size_t row = (size_t)(e0 + lane);
+        float qa;
+        gp_softmax_argmax(base + L.a_off[nl] + lane * L.a_stride[nl], n_out, drow, &qa);
+        const int a = min(max(action[row], 0), n_out - 1);
+        qa = drow[a];
+        const float d = qa - y[row];
+        float dq;
+        if (loss_kind == GL_LOSS_MSE) {
+          ls = d * d;
+          dq = 2.0f * d / (float)n;
+        } else {                                   // nn.SmoothL1Loss(), beta 1 (= nn.HuberLoss(), delta 1)
+          ls = fabsf(d) < 1.0f ? 0.5f * d * d : fabsf(d) - 0.5f;
+          dq = fminf(fmaxf(d, -1.0f), 1.0f) / (float)n;
+        }
+        const float s = dq * qa;                   // dL/dx_j = dL/dq_a q_a ([a == j] - q_j)
+        for (int j = 0; j < n_out; j++) drow[j] = s * ((j == a ? 1.0f : 0.0f) - drow[j]);
+        for (int j = n_out; j < wd; j++) drow[j] = 0.0f;
+      } else {
+        for (int j = 0; j < wd; j++) drow[j] = 0.0f;
+      }
+      row_loss[lane] = ls;
+    }
+  }
+  __syncthreads();
+  if (lane == 0) {
+    float s = 0.0f;
+    for (int r = 0; r < GP_TILE; r++) s += row_loss[r];
+    tile_loss[blockIdx.x] = s;
+  }
+
+  // ---- backward
+  for (int l = nl - 1; l >= 0; l--) {
+    const float* __restrict__ W = params + P.woff[l];
+    const int kpad = P.kpad[l], ksteps = kpad >> 2;
+    const float* A = base + L.a_off[l];
+    const int Sa = L.a_stride[l];
+    const float* D = base + L.d_off[cur];
+    // dW in packed order
+    const int km = 4 * (nn & 3) + (nn >> 2);       // the k (within 16) that product row m = nn stands for
+    for (int t = 0; t < P.tiles[l]; t++)
+      for (int s0 = 0; s0 < ksteps; s0 += 4) {
+        gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+        const int k = 4 * s0 + km;
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) {
+          const int i = 4 * ch + g;
+          const float a = k < kpad ? A[i * Sa + k] : 0.0f;
+          const float b = D[i * Sd + 16 * t + nn];
+          c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          if (s0 + r < ksteps) part[P.woff[l] + ((long long)t * ksteps + s0 + r) * 64 + lane] = c[r];
+      }
+    // db
+    for (int j = lane; j < P.tiles[l] * 16; j += 64) {
+      float s = 0.0f;
+      for (int i = 0; i < GP_TILE; i++) s += D[i * Sd + j];
+      part[P.boff[l] + j] = s;
+    }
+    if (l == 0) break;
+    // the deltas of the layer below, through W and the ReLU that made A
+    float* Dn = base + L.d_off[cur ^ 1];
+    const int wprev = P.tiles[l - 1] * 16;
+    const int jmax = (P.width[l + 1] + 3) & ~3;    // (the deltas of padded columns are 0)
+    for (int kb = 0; kb < wprev; kb += 16) {
+      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+      const int k = kb + nn;
+      for (int j0 = 0; j0 < jmax; j0 += 4) {
+        const int j = j0 + g;
+        const float a = D[nn * Sd + j];
+        const float b = k < kpad ? W[((size_t)(j >> 4) * ksteps + (k >> 2)) * 64 + (k & 3) * 16 + (j & 15)] : 0.0f;
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int i = 4 * g + r;
+        Dn[i * Sd + k] = A[i * Sa + k] > 0.0f ? c[r] : 0.0f;
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+
+// what one launch of gm_learn_step_kernel does, in this order, per packed element
+struct GlStepArgs {
+  int do_sum;            // grad = sum over tiles of the partials, in tile order; thread 0: the mean loss
+  int do_step;           // clamp, then Adam / AdamW on p, m, v, vmax
+  int do_soft;           // target <- tau p + (1 - tau) target
+  int n_tiles, n;
+  long long total;
+  const float* partials;
+  const float* tile_loss;
+  float* grad;
+  float* loss;           // [1]
+  float* loss_out;       // [1] or NULL: a second copy (gm_learner_train's losses[u])
+  float* p;
+  float* m;
+  float* v;
+  float* vmax;
+  float* target;
+  float tau;
+  GlOpt opt;
+};
+
+__global__ __launch_bounds__(256) void gm_learn_step_kernel(GlStepArgs a) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.total) return;
+  float g = 0.0f;
+  if (a.do_sum) {
+    for (int t = 0; t < a.n_tiles; t++) g += a.partials[(size_t)t * a.total + i];
+    a.grad[i] = g;             // the raw gradient: kept, readable (gm_learner_read)
+    if (i == 0) {
+      float s = 0.0f;
+      for (int t = 0; t < a.n_tiles; t++) s += a.tile_loss[t];
+      s = s / (float)a.n;
+      a.loss[0] = s;
+      if (a.loss_out) a.loss_out[0] = s;
+    }
+  } else if (a.do_step) {
+    g = a.grad[i];
+  }
+  float p = a.p[i];
+  if (a.do_step) {
+    if (a.opt.clamp > 0.0f) g = fminf(fmaxf(g, -a.opt.clamp), a.opt.clamp);   // clip_grad_value_
+    float m = a.m[i], v = a.v[i], vmax = a.vmax[i];
+    p = gl_adam(p, g, m, v, vmax, a.opt);
+    a.p[i] = p;
+    a.m[i] = m;
+    a.v[i] = v;
+    a.vmax[i] = vmax;
+  }
+  if (a.do_soft) a.target[i] = gl_soft(p, a.target[i], a.tau);
+}

@@ -11,7 +11,7 @@ from ._lib import (load_library, Settings, ModelParams, Object, Spawn, SpawnPara
                    SENSORS, LIB_PATH, env_state_dtype, env_state_view)
 from .settings import canonical_settings, disable_noise, MAX_EPISODE_STEPS
 from .env import BatchedGripperEnv, spawn_draws, spawn_int, random_fractions
-from .policy import DevicePolicy, ReplayBuffer, eps_threshold
+from .policy import DevicePolicy, DeviceLearner, ReplayBuffer, eps_threshold, dqn_opt, dqn_opt_default
 from .ppo import DeviceActorCritic, TrajectoryBuffer
 from .scripted import GraspScript, in_use_actions
 
@@ -21,5 +21,6 @@ __all__ = ["load_library", "Settings", "ModelParams", "Object", "Spawn", "SpawnP
            "default_settings", "make_object_set", "canonical_settings", "disable_noise",
            "BatchedGripperEnv", "spawn_draws", "spawn_int", "random_fractions", "MAX_EPISODE_STEPS", "BINARY_EVENTS",
            "LINEAR_EVENTS", "ACTION_KINDS", "SENSORS", "LIB_PATH", "DevicePolicy", "ReplayBuffer", "eps_threshold",
+           "DeviceLearner", "dqn_opt", "dqn_opt_default",
            "DeviceActorCritic", "TrajectoryBuffer",
            "GraspScript", "in_use_actions", "env_state_dtype", "env_state_view"]

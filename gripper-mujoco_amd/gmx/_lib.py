@@ -146,6 +146,19 @@ class Calibration(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DqnOpt(C.Structure):
+    """gm_dqn_opt (include/gripper_mi355x.h): the DQN learner's optimiser and loss options."""
+    _fields_ = [("optimiser", C.c_int32), ("amsgrad", C.c_int32), ("loss", C.c_int32), ("pad", C.c_int32),
+                ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("grad_clamp", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+OPT_ADAM, OPT_ADAMW = 0, 1
+LOSS_SMOOTH_L1, LOSS_MSE = 0, 1
+
 CAL_TIMESTEP, CAL_GAUGES, CAL_REFERENCE_RETRY = 1, 2, 4
 
 
@@ -195,7 +208,7 @@ def load_library(path: str | None = None):
             "(run `python -c 'import __graft_entry__ as g; g.build()'` from the repo root)")
     lib = C.CDLL(p)
     _declare(lib)
-    sizes = {0: Settings, 3: Object, 4: Spawn, 5: ModelParams, 6: SpawnParams, 7: Calibration}
+    sizes = {0: Settings, 3: Object, 4: Spawn, 5: ModelParams, 6: SpawnParams, 7: Calibration, 8: DqnOpt}
     for which, cls in sizes.items():
         n = lib.gm_struct_size(which)
         if n < 0 and os.environ.get("GM_LIB"):
@@ -289,7 +302,20 @@ def _declare(lib):
         "gm_replay_indices": (i32, [C.c_int64, i32, C.c_uint64, C.c_uint64, i32p]),
         "gm_replay_sample": (i32, [vp, vp, C.c_int64, i32, C.c_uint64, C.c_uint64, vp]),
         "gm_policy_td_target": (i32, [vp, vp, vp, i32, C.c_float, i32, vp, vp]),
-        "gm_ac_create": (i32, [vp, i32p, i32, i32p, i32, f32p, C.POINTER(vp)]),
+        "gm_dqn_opt_default": (None, [vp]),
+        "gm_learner_create": (i32, [vp, vp, C.POINTER(vp)]),
+        "gm_learner_destroy": (None, [vp]),
+        "gm_learner_grad": (i32, [vp, vp, vp, i32]),
+        "gm_learner_step": (i32, [vp]),
+        "gm_learner_read": (i32, [vp, f32p, f32p]),
+        "gm_learner_get_state": (i32, [vp, C.POINTER(C.c_int64), f32p, f32p, f32p]),
+        "gm_learner_set_state": (i32, [vp, C.POINTER(C.c_int64), f32p, f32p, f32p]),
+        "gm_policy_get_params": (i32, [vp, f32p]),
+        "gm_policy_get_packed": (i32, [vp, f32p]),
+        "gm_policy_soft_update": (i32, [vp, vp, C.c_float]),
+        "gm_learner_train": (i32, [vp, vp, vp, C.c_int64, i32, C.c_uint64, C.c_uint64, i32, C.c_float, i32, i32,
+                                   C.c_float, vp]),
+        "gm_ac_create": (i32,[vp, i32p, i32, i32p, i32, f32p, C.POINTER(vp)]),
         "gm_ac_destroy": (None, [vp]),
         "gm_ac_set_params": (i32, [vp, f32p]),
         "gm_ac_pack": (C.c_int64, [i32p, i32, i32p, i32, f32p, f32p, C.POINTER(C.c_int64)]),

@@ -15,8 +15,17 @@ The data plumbing of training sits next to it, on the device too:
     around an env-step or inside the fused launch (rollout(replay=buf)), sampled without
     replacement by ReplayBuffer.sample;
   - optimise_model's TD target (DQN.py:294-315), plain or double, as DevicePolicy.td_target.
-There is no trainer here: loss, backward, optimiser and the soft target update are the user's
-torch code, which hands new weights back with DevicePolicy.set_params().
+The learning step is here as well:
+  - optimise_model from the loss on (DQN.py:317-327: smooth-L1 / MSE loss, backward,
+    clip_grad_value_, Adam / AdamW step) as DeviceLearner.grad / step, on the packed device
+    weights the rollout reads, and update_step's soft target update (DQN.py:352-360) as
+    DevicePolicy.soft_update;
+  - DeviceLearner.train enqueues whole updates (sample -> TD target -> gradient -> step -> soft
+    update) with no host synchronisation between them, so a training loop is
+    rollout(replay=buf) followed by learner.train(buf, n_updates) and no weight crosses the bus.
+DevicePolicy.get_params() reads the device's weights back; set_params() remains for weights that
+come from elsewhere (a checkpoint, a torch optimiser of the user's own).  RMSprop and
+update_episode's hard-copy schedule are not here; a hard copy is soft_update(online, tau=1).
 """
 from __future__ import annotations
 
@@ -25,7 +34,7 @@ import math
 
 import numpy as np
 
-from ._lib import load_library
+from ._lib import load_library, DqnOpt, OPT_ADAM, OPT_ADAMW, LOSS_SMOOTH_L1, LOSS_MSE
 
 CANONICAL_HIDDEN = (150, 100, 50)
 
@@ -309,10 +318,162 @@ class DevicePolicy:
         torch.cuda.synchronize(dev)     # the env's stream, before torch reads the results
         return y, v
 
+    def get_params(self) -> np.ndarray:
+        """The device's weights in init_params' flat order (the inverse of set_params); also
+        refreshes self.params, which a DeviceLearner's steps leave behind."""
+        out = np.empty(self.params.size, dtype=np.float32)
+        self._check(self.lib.gm_policy_get_params(self._p, out.ctypes.data_as(C.POINTER(C.c_float))),
+                    "gm_policy_get_params")
+        self.params = out
+        return out.copy()
+
+    def get_packed(self) -> np.ndarray:
+        """The device's weights as stored (pack()'s layout, padding entries included)."""
+        out = np.empty(pack(self.sizes, self.params).size, dtype=np.float32)
+        self._check(self.lib.gm_policy_get_packed(self._p, out.ctypes.data_as(C.POINTER(C.c_float))),
+                    "gm_policy_get_packed")
+        return out
+
+    def soft_update(self, online: "DevicePolicy", tau: float):
+        """update_step's soft target update on the device: self <- tau online + (1 - tau) self.
+        tau = 1 is the hard copy."""
+        self._check(self.lib.gm_policy_soft_update(self._p, online._p, C.c_float(tau)), "gm_policy_soft_update")
+
     def close(self):
         if self._p:
             self.lib.gm_policy_destroy(self._p)
             self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+LEARNER_MAX_BATCH = 256     # GM_LEARNER_MAX_BATCH
+
+_OPTIMISERS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW}
+_LOSSES = {"smoothl1loss": LOSS_SMOOTH_L1, "huber": LOSS_SMOOTH_L1, "mseloss": LOSS_MSE}
+
+
+def dqn_opt(learning_rate: float = 1e-4, adam_beta1: float = 0.9, adam_beta2: float = 0.999, optimiser: str = "adamW",
+            grad_clamp_value=100, loss_criterion: str = "smoothL1Loss", eps: float = 1e-8, weight_decay=None,
+            amsgrad=None) -> DqnOpt:
+    """Agent_DQN.Parameters' optimiser and loss options (DQN.py:68-92) as Agent_DQN.init hands them
+    to torch (:130-151), as a gm_dqn_opt: "adam" is torch.optim.Adam(lr, betas) -- weight_decay 0,
+    no amsgrad; "adamW" is torch.optim.AdamW(lr, betas, amsgrad=True) -- weight_decay 0.01, torch's
+    default.  weight_decay / amsgrad, when given, override that.  "Huber" (nn.HuberLoss(), delta 1)
+    is "smoothL1Loss" (beta 1); grad_clamp_value None disables the clamp.  No GPU needed."""
+    name = str(optimiser).lower()
+    if name not in _OPTIMISERS:
+        raise ValueError(f"optimiser {optimiser!r}: 'adam' or 'adamW' expected (RMSprop is not on the device)")
+    if str(loss_criterion).lower() not in _LOSSES:
+        raise ValueError(f"loss_criterion {loss_criterion!r}: 'smoothL1Loss', 'MSELoss' or 'Huber' expected")
+    o = DqnOpt()
+    o.optimiser = _OPTIMISERS[name]
+    o.amsgrad = int(name == "adamw" if amsgrad is None else bool(amsgrad))
+    o.loss = _LOSSES[str(loss_criterion).lower()]
+    o.lr, o.beta1, o.beta2, o.eps = float(learning_rate), float(adam_beta1), float(adam_beta2), float(eps)
+    o.weight_decay = float((0.01 if name == "adamw" else 0.0) if weight_decay is None else weight_decay)
+    o.grad_clamp = 0.0 if grad_clamp_value is None else float(grad_clamp_value)
+    return o
+
+
+def dqn_opt_default() -> DqnOpt:
+    """gm_dqn_opt_default: the library's own defaults (equal to dqn_opt()'s)."""
+    o = DqnOpt()
+    load_library().gm_dqn_opt_default(C.byref(o))
+    return o
+
+
+class DeviceLearner:
+    """Agent_DQN.optimise_model from the loss on and the soft target update, on the device weights
+    of `policy` (the online net) and `target`.  Options are Agent_DQN.Parameters' names
+    (learning_rate, adam_beta1, adam_beta2, optimiser, grad_clamp_value, loss_criterion; see
+    dqn_opt) plus soft_target_tau, gamma, use_double_dqn, soft_target_update and mask_terminal,
+    which train() uses."""
+
+    def __init__(self, policy: DevicePolicy, target: DevicePolicy | None = None, soft_target_tau: float = 0.05,
+                 gamma: float = 0.99, use_double_dqn: bool = False, soft_target_update: bool = True,
+                 mask_terminal: bool = False, **opts):
+        self.policy, self.target = policy, target
+        self.env, self.lib = policy.env, policy.lib
+        self.tau, self.gamma = float(soft_target_tau), float(gamma)
+        self.double, self.soft, self.mask_terminal = bool(use_double_dqn), bool(soft_target_update), bool(mask_terminal)
+        self.opt = dqn_opt(**opts)
+        self._l = C.c_void_p()
+        self._check(self.lib.gm_learner_create(policy._p, C.byref(self.opt), C.byref(self._l)), "gm_learner_create")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(self.lib.gm_last_error(self.env.ctx).decode() or f"{what} failed ({rc})")
+
+    def grad(self, batch: dict, y):
+        """loss.backward() for a sampled batch (state and action are read) and its TD targets y
+        (a device tensor [batch]): leaves the raw gradient and the mean loss on the device."""
+        import torch
+        n = int(y.shape[0])
+        b = _batch_struct(batch)
+        torch.cuda.synchronize(y.device)     # torch-side writes to the batch and y
+        self._check(self.lib.gm_learner_grad(self._l, C.byref(b), C.c_void_p(y.data_ptr()), n), "gm_learner_grad")
+        torch.cuda.synchronize(y.device)     # the env's stream, before torch reuses the tensors
+
+    def step(self):
+        """clip_grad_value_ and optimiser.step() on the held gradient, in place on the policy."""
+        self._check(self.lib.gm_learner_step(self._l), "gm_learner_step")
+
+    def read(self):
+        """(gradient in init_params' flat order, mean loss) of the last grad() / update."""
+        g = np.empty(self.policy.params.size, dtype=np.float32)
+        loss = C.c_float()
+        self._check(self.lib.gm_learner_read(self._l, g.ctypes.data_as(C.POINTER(C.c_float)), C.byref(loss)),
+                    "gm_learner_read")
+        return g, float(loss.value)
+
+    def state(self) -> dict:
+        """The optimiser's state in flat order, like optimiser.state_dict()'s tensors: step,
+        exp_avg, exp_avg_sq, max_exp_avg_sq."""
+        f32p = C.POINTER(C.c_float)
+        n = self.policy.params.size
+        step = C.c_int64()
+        out = {k: np.empty(n, dtype=np.float32) for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")}
+        self._check(self.lib.gm_learner_get_state(self._l, C.byref(step), *(out[k].ctypes.data_as(f32p) for k in out)),
+                    "gm_learner_get_state")
+        return dict(step=int(step.value), **out)
+
+    def load_state(self, state: dict):
+        f32p = C.POINTER(C.c_float)
+        n = self.policy.params.size
+        arrs = [np.ascontiguousarray(as_f32(state[k]), np.float32).ravel()
+                for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")]
+        if any(a.size != n for a in arrs):
+            raise ValueError(f"{n} entries per moment expected")
+        step = C.c_int64(int(state["step"]))
+        self._check(self.lib.gm_learner_set_state(self._l, C.byref(step), *(a.ctypes.data_as(f32p) for a in arrs)),
+                    "gm_learner_set_state")
+
+    def train(self, buf: ReplayBuffer, n_updates: int, batch_size: int = 128, seed: int = 0, draw0: int = 0):
+        """n_updates of Agent_DQN.update_step's learning part, enqueued back to back: sample(draw0 + u)
+        -> TD target -> gradient -> optimiser step -> soft target update.  Returns the mean loss of
+        every update as a device tensor [n_updates]."""
+        import torch
+        dev = buf.state.device
+        losses = torch.empty((int(n_updates),), dtype=torch.float32, device=dev)
+        r = buf.struct()
+        tau = self.tau if (self.soft and self.target is not None) else 0.0
+        torch.cuda.synchronize(dev)     # torch-side writes to the memory (tests), the allocation
+        self._check(self.lib.gm_learner_train(
+            self._l, self.target._p if self.target is not None else None, C.byref(r), len(buf), int(batch_size),
+            C.c_uint64(seed), C.c_uint64(draw0), int(n_updates), C.c_float(self.gamma), int(self.double),
+            int(self.mask_terminal), C.c_float(tau), C.c_void_p(losses.data_ptr())), "gm_learner_train")
+        torch.cuda.synchronize(dev)     # the env's stream, before torch reads the losses
+        return losses
+
+    def close(self):
+        if self._l:
+            self.lib.gm_learner_destroy(self._l)
+            self._l = C.c_void_p()
 
     def __del__(self):
         try:

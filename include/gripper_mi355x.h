@@ -332,7 +332,8 @@ typedef struct gm_ctx gm_ctx;
 const char* gm_version(void);
 int  gm_device_count(void);
 /* sizes of the interface structs (0 settings, 1 model, 2 config, 3 object, 4 spawn,
- * 5 model params, 6 spawn params, 7 calibration) so bindings can verify their layouts */
+ * 5 model params, 6 spawn params, 7 calibration, 8 DQN optimiser options) so bindings can verify
+ * their layouts */
 int64_t gm_struct_size(int which);
 /* model summary: nq, nv, nbody, ngeom, npair, n_seg, dof_base, dof_palm, dof_obj,
  * dof_pris[3], dof_rev[3], dof_seg[3], nlock, nM (tree-sparse M nonzeros)  (20 int32) */
@@ -769,6 +770,73 @@ int  gm_replay_sample(gm_ctx* ctx, const gm_replay* replay, int64_t size, int ba
  * Reads batch->next_state, reward and end; y, next_value (v; may be NULL): device [n]. */
 int  gm_policy_td_target(gm_policy* target, gm_policy* online, const gm_replay_batch* batch, int n, float gamma,
                          int mask_terminal, float* y, float* next_value);
+
+/* ---- DQN learner: backward, Adam / AdamW step and the soft target update ----
+ * Agent_DQN.optimise_model from the loss on (rl/agents/DQN.py:317-327: criterion, backward,
+ * clip_grad_value_, optimiser.step) and update_step's soft target update (:352-360), on the packed
+ * weights where the rollout reads them: gradients and moments live in gm_policy_pack's layout, the
+ * step updates the online policy in place, nothing is repacked and no weight crosses the bus.
+ * f32; no float atomics: the same call on the same inputs gives the same bits.  RMSprop (:130-132)
+ * and update_episode's hard-copy schedule are not here; a hard copy is gm_policy_soft_update with
+ * tau = 1. */
+#define GM_OPT_ADAM        0    /* torch.optim.Adam  (DQN.py:133-137) */
+#define GM_OPT_ADAMW       1    /* torch.optim.AdamW (DQN.py:138-143) */
+#define GM_LOSS_SMOOTH_L1  0    /* nn.SmoothL1Loss(), beta 1 = nn.HuberLoss(), delta 1 (DQN.py:146-151) */
+#define GM_LOSS_MSE        1    /* nn.MSELoss() */
+#define GM_LEARNER_MAX_BATCH 256
+typedef struct gm_dqn_opt {     /* Agent_DQN.Parameters (DQN.py:68-92) as init() hands them to torch (:130-151);
+                                   doubles, as torch keeps its hyperparameters */
+  int32_t optimiser;            /* GM_OPT_* */
+  int32_t amsgrad;
+  int32_t loss;                 /* GM_LOSS_* */
+  int32_t pad;
+  double  lr, beta1, beta2, eps, weight_decay;
+  double  grad_clamp;           /* clip_grad_value_'s bound (DQN.py:325-326); <= 0: none */
+} gm_dqn_opt;
+/* Parameters' defaults as torch resolves them: AdamW, lr 1e-4, betas (0.9, 0.999), eps 1e-8,
+ * weight_decay 0.01 (torch's AdamW default), amsgrad on, smooth-L1, clamp 100 */
+void gm_dqn_opt_default(gm_dqn_opt* out);
+/* A learner for `online`, on its context: owns the per-tile partial gradients, the summed gradient,
+ * exp_avg / exp_avg_sq / max_exp_avg_sq (zero), the step count (0) and the scratch, sized for
+ * batches of up to GM_LEARNER_MAX_BATCH rows.  Destroy it before `online`. */
+typedef struct gm_learner gm_learner;
+int  gm_learner_create(gm_policy* online, const gm_dqn_opt* opt, gm_learner** out);
+void gm_learner_destroy(gm_learner* l);
+/* loss.backward() (DQN.py:292, 319-323) for the first n rows of a batch: q_a = softmax(net(state))
+ * [action], loss = mean criterion(q_a, y); leaves the raw, unclamped gradient (packed) and the mean
+ * loss on the device.  Reads batch->state and batch->action; y: device [n].  n > GM_LEARNER_MAX_BATCH
+ * is GM_E_ARG. */
+int  gm_learner_grad(gm_learner* l, const gm_replay_batch* batch, const float* y, int n);
+/* clip_grad_value_ and optimiser.step() (DQN.py:325-327) on the held gradient, in place on the
+ * online policy's device weights; the step count goes up by one. */
+int  gm_learner_step(gm_learner* l);
+/* The held gradient in gm_policy_create's flat order and the mean loss (host pointers; either may
+ * be NULL). */
+int  gm_learner_read(gm_learner* l, float* grad_flat, float* loss);
+/* optimiser.state_dict()'s tensors in flat order (DQN.py saves optimiser_state_dict with the
+ * agent): step, exp_avg, exp_avg_sq, max_exp_avg_sq.  Host pointers; any may be NULL. */
+int  gm_learner_get_state(gm_learner* l, int64_t* step, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq);
+int  gm_learner_set_state(gm_learner* l, const int64_t* step, const float* exp_avg, const float* exp_avg_sq,
+                          const float* max_exp_avg_sq);
+/* The inverse of gm_policy_set_params: the device weights in flat order (host pointer). */
+int  gm_policy_get_params(gm_policy* p, float* flat);
+/* The device weights as stored, gm_policy_pack's layout and count (host pointer): the padding
+ * entries included, which must stay exactly 0 under every update. */
+int  gm_policy_get_packed(gm_policy* p, float* packed);
+/* target <- tau online + (1 - tau) target (DQN.py:352-360) on the device; the two policies need
+ * the same layer sizes and the same context.  tau = 1 copies online bit for bit. */
+int  gm_policy_soft_update(gm_policy* target, gm_policy* online, float tau);
+/* n_updates learning steps enqueued with no host synchronisation between them: for u = 0 ..
+ * n_updates - 1
+ *   gm_replay_sample(size, batch, seed, draw0 + u) into the learner's own batch arrays
+ *   -> gm_policy_td_target(target, double_dqn ? online : NULL, gamma, mask_terminal)
+ *   -> gm_learner_grad -> gm_learner_step -> gm_policy_soft_update(target, online, tau)
+ * the same kernels in the same order as the calls, so every result equals theirs bit for bit.
+ * target = NULL: the online net is its own target (then tau must be <= 0); tau <= 0 skips the
+ * soft update.  losses: device [n_updates] (the mean loss of every update) or NULL. */
+int  gm_learner_train(gm_learner* l, gm_policy* target, const gm_replay* replay, int64_t size, int batch,
+                      uint64_t seed, uint64_t draw0, int n_updates, float gamma, int double_dqn,
+                      int mask_terminal, float tau, float* losses);
 
 /* ---- on-device PPO actor-critic, trajectory buffer and GAE ----
  * MLPActorCriticPG.step (rl/agents/PolicyGradient.py:522-528) and Agent_PPO.select_action

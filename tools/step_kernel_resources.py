@@ -25,7 +25,8 @@ LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 SECTIONS = (".text", ".rodata", ".note")
 FUNCS = ("ac_rollout_driver", "replay_record", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel", "gm_policy_kernel",
-         "gm_td_target_kernel", "gm_replay_sample_kernel", "substep_loop", "reset_env", "driver_actions")
+         "gm_td_target_kernel", "gm_replay_sample_kernel", "gm_learn_grad_kernel", "gm_learn_step_kernel",
+         "substep_loop", "reset_env", "driver_actions")
 
 
 def tool(name, *args):
