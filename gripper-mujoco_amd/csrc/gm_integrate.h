@@ -15,7 +15,8 @@ __device__ __forceinline__ real* duo_ef() {
 
 // ============================================================ integrate
 template <int CL, bool CAL, bool DUO = false>
-__device__ __forceinline__ void integrate(SharedT<CL>& S, const gm_model* __restrict__ m, const GmTopo* __restrict__ T, int lane) {
+__device__ __forceinline__ void integrate(SharedT<CL>& S, const gm_model* __restrict__ m, const GmTopo* __restrict__ T, int lane,
+                                          bool prof = false) {
   const real h = CAL ? S.s.dt : m->timestep;
   if constexpr (CAL) {
     // mj_checkAcc's mjWARN_BADQACC (is_sim_unstable, myfunctions.cpp:4233-4242): a
@@ -39,7 +40,21 @@ __device__ __forceinline__ void integrate(SharedT<CL>& S, const gm_model* __rest
       euler_solve<CL>(S, T, h, ln, L, ef[CL * 64 + ln], ef[(CL + 1) * 64 + ln], ef[64 * (CL + 2)]);
     }
   } else {
-    if (mj) euler_damping<CL>(S, T, h, fresh_lane());
+    if (mj) {
+      // euler_damping, with the profiled instance's marks between its halves: the Euler
+      // factor's and the Euler solve's clocks go to the upper halves of two counter columns
+      // (gmx.env integrate_split); the rest of the stage is PH(8) minus the two
+      unsigned long long t0 = prof ? clock64() : 0;
+#define GM_PH_HI(k) do { if (__builtin_expect(prof, 0)) { unsigned long long t_ = clock64(); \
+                         if (lane == 0) S.tph[k] += (t_ - t0) << 32; t0 = t_; } } while (0)
+      const int ln = fresh_lane();
+      real L[CL + 1], lb, invd;
+      const real sch = euler_factor<CL>(S, T, h, ln, L, lb, invd);
+      GM_PH_HI(28);
+      euler_solve<CL>(S, T, h, ln, L, lb, invd, sch);
+      GM_PH_HI(31);
+#undef GM_PH_HI
+    }
   }
   if (lane < T->nv) S.s.qvel[lane] += h * (mj ? S.xs[lane] : S.qacc[lane]);
   GM_WAVE_SYNC();

@@ -40,7 +40,7 @@ __device__ __forceinline__ void physics_substep_body(SharedT<CL>& S, const gm_mo
   PH(5);
   newton_solve<CL, CAL, DUO>(S, m, T, fresh_lane(), prof);
   PH(6);
-  integrate<CL, CAL, DUO>(S, m, T, fresh_lane());
+  integrate<CL, CAL, DUO>(S, m, T, fresh_lane(), prof);
   PH(8);
 }
 

@@ -448,4 +448,10 @@ class BatchedGripperEnv:
         # env-step whose first Newton point took the decoupled path (newton_point_decoupled)
         self.decoupled_points = (ph[:, 27] >> np.uint64(32)).astype(np.int64)
         ph[:, 27] &= np.uint64(0xFFFFFFFF)
+        # ... and so do two counter columns: the clocks of integrate's Euler factor and Euler
+        # solve (one-wave kernel); the rest of "integrate" is qvel / qpos and the object's step
+        self.integrate_split = np.stack([ph[:, self.PH_NEFC] >> np.uint64(32), ph[:, self.PH_LS] >> np.uint64(32)],
+                                        axis=1).astype(np.int64)
+        for k in (self.PH_NEFC, self.PH_LS):
+            ph[:, k] &= np.uint64(0xFFFFFFFF)
         return ph

@@ -35,6 +35,7 @@ for t in range(MAX_EP):
         env.lib.gm_reset(env.ctx, np.ascontiguousarray(m.astype(np.uint8)).ctypes.data_as(C.POINTER(C.c_uint8)), None)
     drive()
 tot = np.zeros(env.N_PHASE)
+split = np.zeros(2)
 dropped = 0
 for t in range(3):
     ph = drive(True).astype(np.float64)
@@ -43,7 +44,9 @@ for t in range(3):
     ok = (ph[:, :25] < 2.0 ** 48).all(axis=1)
     dropped += int((~ok).sum())
     tot += ph[ok].mean(axis=0)
+    split += env.integrate_split[ok].mean(axis=0)
 tot /= 3
+split /= 3
 if dropped:
     print(f"({dropped} env rows with a wrapped clock difference left out of the means)")
 S = 63
@@ -57,6 +60,9 @@ for k, name in enumerate(env.PHASES):
         print(f"  {name:18s} {tot[k]:10.0f} cyc/env-step  (= {tot[k] / S:.0f} per substep)")
     else:
         print(f"  {name:18s} {tot[k] / S:10.0f} cyc/substep  {100 * tot[k] / allc:5.1f}%")
+ik = env.PHASES.index("integrate")
+print(f"  integrate split: Euler factor {split[0] / S:.0f}, Euler solve {split[1] / S:.0f}, "
+      f"qvel / qpos + the object's step {(tot[ik] - split.sum()) / S:.0f} cyc/substep")
 print(f"  whole env-step on one wave {tot[23]:.3e} cyc")
 print(f"  rows per substep {tot[env.PH_NEFC] / S:.1f}; Newton iterations per solve {tot[env.PH_NEWTON] / S:.3f}; "
       f"line-search evals per solve {tot[env.PH_LS] / S:.3f}; substeps running MPR {tot[env.PH_MPR] / S:.3f}")
