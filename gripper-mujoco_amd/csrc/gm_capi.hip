@@ -24,6 +24,7 @@
 #include "gm_replay.hip"
 #include "gm_learn.hip"
 #include "gm_ac.hip"
+#include "gm_ppo_learn.hip"
 
 // calibration translation unit (gm_calib.hip)
 hipError_t gm_cal_launch_step(int n_seg, int n_envs, hipStream_t st, GmEnvState* states, const gm_model* m,
@@ -1298,26 +1299,7 @@ struct gm_policy {
   DevBuf<GrArgs> d_replay;     // gm_policy_rollout_replay's launch arguments
 };
 
-static int64_t policy_layout(const int32_t* sizes, int n_sizes, GpNet* net) {
-  if (!sizes || n_sizes < 2 || n_sizes - 1 > GP_MAX_LAYERS) return -1;
-  GpNet P{};
-  P.n_layers = n_sizes - 1;
-  long long off = 0;
-  for (int l = 0; l < n_sizes; l++) {
-    if (sizes[l] < 1 || sizes[l] > GP_MAX_WIDTH) return -1;
-    P.width[l] = sizes[l];
-  }
-  for (int l = 0; l < P.n_layers; l++) {
-    P.kpad[l] = (P.width[l] + 3) & ~3;
-    P.tiles[l] = (P.width[l + 1] + 15) / 16;
-    P.woff[l] = off;
-    off += (long long)P.tiles[l] * (P.kpad[l] / 4) * 64;
-    P.boff[l] = off;
-    off += (long long)P.tiles[l] * 16;
-  }
-  if (net) *net = P;
-  return off;
-}
+static int64_t policy_layout(const int32_t* sizes, int n_sizes, GpNet* net) { return gl_layout(sizes, n_sizes, net); }
 
 extern "C" {
 
@@ -1851,21 +1833,7 @@ struct gm_ac {
 static_assert(GA_MAX_ACT >= GM_ACTION_CODE_COUNT, "the sampler's rows hold every action");
 
 static int64_t ac_layout(const int32_t* asz, int na, const int32_t* csz, int nc, GaNet* net, int64_t* n_raw) {
-  GaNet N{};
-  const int64_t ta = policy_layout(asz, na, &N.actor);
-  const int64_t tc = policy_layout(csz, nc, &N.critic);
-  if (ta < 0 || tc < 0) return -1;
-  N.act_actor = N.act_critic = GP_ACT_TANH;
-  N.critic_off = ta;
-  N.log_std_off = ta + tc;
-  if (net) *net = N;
-  if (n_raw) {
-    int64_t r = 0;
-    for (int l = 0; l + 1 < na; l++) r += (int64_t)asz[l + 1] * asz[l] + asz[l + 1];
-    for (int l = 0; l + 1 < nc; l++) r += (int64_t)csz[l + 1] * csz[l] + csz[l + 1];
-    *n_raw = r + asz[na - 1];
-  }
-  return ta + tc + asz[na - 1];
+  return gq_layout(asz, na, csz, nc, net, n_raw);
 }
 
 // the device-side view of a caller's trajectory buffer
@@ -2021,6 +1989,365 @@ int gm_ac_gae(gm_ctx* c, const gm_ac_traj* traj, int n_steps, float gamma, float
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, launch_per_env(c, gm_ac_gae_kernel, traj->rew, traj->val, traj->end, traj->boot, traj->last_val, c->n_envs,
                            n_steps, gamma, lam, adv, ret));
+  return GM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- on-device PPO learner
+struct gm_ppo_learner {
+  gm_ctx* ctx = nullptr;
+  gm_ac* ac = nullptr;
+  gm_ppo_opt opt{};
+  int groups = 0;
+  GlPlan plan_pi{}, plan_vf{};
+  int64_t step_pi = 0, step_vf = 0;         // optimiser steps taken
+  DevBuf<float> d_partials;                 // [groups][total] one running gradient per workgroup
+  DevBuf<float> d_wg;                       // [groups][GQ_INFO]
+  DevBuf<float> d_grad, d_m, d_v, d_vmax;   // [total], packed order; policy entries pi's, critic entries vf's
+  DevBuf<float> d_scalars;                  // [3][GQ_SCALARS]: the held gradient's, update's first and last
+  DevBuf<int32_t> d_stop;                   // [2] the KL stop's latch, policy iterations that stepped
+  DevBuf<float> d_spill;                    // [groups][spill_stride] the gradient kernels' rows where they do not fit LDS
+  long long spill_stride = 1;
+  DevBuf<float> d_adv, d_ret;               // gm_ppo_learner_update's advantages and returns
+  size_t rows_cap = 0;
+};
+
+// the optimiser's launch arguments of step t of pi (policy) or vf, through the DQN learner's rule
+static GlOpt ppo_learner_opt(const gm_ppo_opt& o, bool policy, int64_t t) {
+  gm_dqn_opt d{};
+  d.optimiser = o.optimiser;
+  d.amsgrad = o.optimiser == GM_OPT_ADAMW;
+  d.lr = policy ? o.learning_rate_pi : o.learning_rate_vf;
+  d.beta1 = o.adam_beta1;
+  d.beta2 = o.adam_beta2;
+  d.eps = 1e-8;
+  d.weight_decay = o.optimiser == GM_OPT_ADAMW ? 0.01 : 0.0;
+  d.grad_clamp = o.grad_clamp_value > 0 ? o.grad_clamp_value : 0.0;
+  return learner_opt(d, t);
+}
+// the gradient kernel of one net over a batch, then the reduce kernel; stop: d_stop inside
+// gm_ppo_learner_update's policy loop, else NULL; first / last: update's info rows or NULL
+static hipError_t ppo_launch_grad(gm_ppo_learner* l, bool policy, const gm_ppo_batch& b, int* stop, float* first,
+                                  float* last) {
+  gm_ctx* c = l->ctx;
+  const gm_ac* p = l->ac;
+  const GaNet& N = p->net;
+  const int n_act = N.actor.width[N.actor.n_layers];
+  GqGradArgs a{};
+  a.obs = b.obs; a.act = b.act; a.logp_old = b.logp; a.adv = b.adv; a.ret = b.ret;
+  a.n = b.n;
+  a.params = p->d_params;
+  a.net = policy ? N.actor : N.critic;
+  a.plan = policy ? l->plan_pi : l->plan_vf;
+  a.net_off = policy ? 0 : N.critic_off;
+  a.net_total = policy ? N.critic_off : N.log_std_off - N.critic_off;
+  a.lds_part = gq_lds_part(a.plan, a.net_total);
+  a.log_std_off = N.log_std_off;
+  a.n_groups = l->groups;
+  a.use_kl = l->opt.use_kl_penalty != 0;
+  a.clip_lo = (float)(1.0 - l->opt.clip_ratio);
+  a.clip_hi = (float)(1.0 + l->opt.clip_ratio);
+  a.beta = (float)l->opt.kl_penalty_coefficient;
+  a.spill = l->d_spill;
+  a.spill_stride = l->spill_stride;
+  a.partials = l->d_partials;
+  a.total = (long long)p->total;
+  a.wg_info = l->d_wg;
+  a.stop = stop;
+  const size_t lds = sizeof(float) * (size_t)(a.plan.total <= GL_ARENA ? a.plan.total + (a.lds_part ? a.net_total : 0) : 0);
+  if (policy)
+    hipLaunchKernelGGL(gm_ppo_grad_pi_kernel, dim3(l->groups), dim3(64), lds, c->stream, a);
+  else
+    hipLaunchKernelGGL(gm_ppo_grad_vf_kernel, dim3(l->groups), dim3(64), lds, c->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const long long tiles = (b.n + GP_TILE - 1) / GP_TILE;
+  const long long ta = N.critic_off, tc = N.log_std_off - N.critic_off;
+  GqReduceArgs r{};
+  r.partials = l->d_partials;
+  r.total = a.total;
+  r.n_parts = (int)std::min<long long>(l->groups, tiles);
+  r.count = policy ? ta + n_act : tc;
+  r.first = policy ? 0 : ta;
+  r.gap_at = policy ? ta : r.count;
+  r.gap_len = policy ? tc : 0;
+  r.grad = l->d_grad;
+  r.wg_info = l->d_wg;
+  r.n = b.n;
+  r.policy = policy;
+  r.use_kl = a.use_kl;
+  r.use_ent = l->opt.use_entropy_regularisation != 0;
+  r.beta = a.beta;
+  r.c_ent = (float)l->opt.entropy_coefficient;
+  r.params = p->d_params;
+  r.log_std_off = N.log_std_off;
+  r.n_act = n_act;
+  r.scalars = l->d_scalars;
+  r.first_out = first;
+  r.last_out = last;
+  r.stop = stop;
+  r.kl_stop = l->opt.max_kl_ratio * l->opt.target_kl;
+  const int threads = 256;
+  hipLaunchKernelGGL(gm_ppo_reduce_kernel, dim3((unsigned)((r.count + threads - 1) / threads)), dim3(threads), 0,
+                     c->stream, r);
+  return hipGetLastError();
+}
+// gm_learn_step_kernel over one optimiser's elements, as step t; skip: the KL stop's latch or NULL
+static hipError_t ppo_launch_step(gm_ppo_learner* l, bool policy, int64_t t, const int* skip) {
+  gm_ctx* c = l->ctx;
+  const GaNet& N = l->ac->net;
+  const long long ta = N.critic_off, tc = N.log_std_off - N.critic_off;
+  const long long first = policy ? 0 : ta;
+  GlStepArgs a{};
+  a.do_step = 1;
+  a.total = policy ? ta + N.actor.width[N.actor.n_layers] : tc;
+  a.gap_at = policy ? ta : 0;
+  a.gap_len = policy ? tc : 0;
+  a.grad = l->d_grad + first;
+  a.p = l->ac->d_params + first;
+  a.m = l->d_m + first;
+  a.v = l->d_v + first;
+  a.vmax = l->d_vmax + first;
+  a.opt = ppo_learner_opt(l->opt, policy, std::max<int64_t>(t, 1));
+  a.skip = skip;
+  const int threads = 256;
+  hipLaunchKernelGGL(gm_learn_step_kernel, dim3((unsigned)((a.total + threads - 1) / threads)), dim3(threads), 0,
+                     c->stream, a);
+  return hipGetLastError();
+}
+static bool ppo_batch_ok(const gm_ppo_batch* b, bool policy) {
+  return b && b->n >= 1 && b->obs && (policy ? (b->act && b->logp && b->adv) : b->ret != nullptr);
+}
+// a packed device array of the blob -> flat host array
+static int ac_unpack(gm_ctx* c, const gm_ac* p, const float* d_packed, float* out) {
+  std::vector<float> packed((size_t)p->total);
+  const int rc = read_back(c, packed.data(), d_packed, sizeof(float) * (size_t)p->total);
+  if (rc != GM_OK) return rc;
+  gq_unpack(p->net, packed.data(), out);
+  return GM_OK;
+}
+
+extern "C" {
+
+void gm_ppo_opt_default(gm_ppo_opt* out) {
+  if (!out) return;
+  gm_ppo_opt o{};
+  o.learning_rate_pi = 3e-4; o.learning_rate_vf = 1e-3; o.gamma = 0.99; o.lam = 0.97; o.clip_ratio = 0.2;
+  o.train_pi_iters = 80; o.train_vf_iters = 80;
+  o.target_kl = 0.01; o.max_kl_ratio = 1.5;
+  o.optimiser = GM_OPT_ADAM;
+  o.use_kl_penalty = 0; o.kl_penalty_coefficient = 0.2;
+  o.use_entropy_regularisation = 0; o.entropy_coefficient = 1e-4;
+  o.adam_beta1 = 0.9; o.adam_beta2 = 0.999;
+  o.grad_clamp_value = 0.0;
+  *out = o;
+}
+
+int gm_ac_adv_normalise(gm_ctx* c, float* adv, int64_t n) {
+  if (!c) return GM_E_ARG;
+  if (!adv || n < 2) return fail(c, GM_E_ARG, "gm_ac_adv_normalise: no array or n < 2 (one value has no standard deviation)");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(gm_ac_adv_normalise_kernel, dim3(1), dim3(1024), 0, c->stream, adv, (long long)n);
+  HIPCHK(c, hipGetLastError());
+  return GM_OK;
+}
+
+int gm_ac_get_params(gm_ac* p, float* flat) {
+  if (!p || !p->ctx || !flat) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  return ac_unpack(c, p, p->d_params, flat);
+}
+
+int gm_ac_get_packed(gm_ac* p, float* packed) {
+  if (!p || !p->ctx || !packed) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  return read_back(c, packed, p->d_params, sizeof(float) * (size_t)p->total);
+}
+
+int gm_ppo_learner_create(gm_ac* ac, const gm_ppo_opt* opt, int n_groups, gm_ppo_learner** out) {
+  if (!ac || !ac->ctx || !out) return GM_E_ARG;
+  gm_ctx* c = ac->ctx;
+  gm_ppo_opt o;
+  gm_ppo_opt_default(&o);
+  if (opt) o = *opt;
+  if (o.optimiser != GM_OPT_ADAM && o.optimiser != GM_OPT_ADAMW)
+    return fail(c, GM_E_ARG, "gm_ppo_learner_create: optimiser must be GM_OPT_ADAM / GM_OPT_ADAMW (RMSprop is not on the device)");
+  if (!(o.learning_rate_pi >= 0) || !(o.learning_rate_vf >= 0) || !(o.adam_beta1 >= 0 && o.adam_beta1 < 1) ||
+      !(o.adam_beta2 >= 0 && o.adam_beta2 < 1) || !(o.clip_ratio >= 0) || o.train_pi_iters < 0 || o.train_vf_iters < 0)
+    return fail(c, GM_E_ARG, "gm_ppo_learner_create: learning rates, clip_ratio, iteration counts >= 0 and betas in [0, 1) expected");
+  if (n_groups < 0 || n_groups > GQ_MAX_GROUPS)
+    return fail(c, GM_E_ARG, "gm_ppo_learner_create: n_groups in 0 (the default) .. " + std::to_string(GQ_MAX_GROUPS) + " expected");
+  HIPCHK(c, hipSetDevice(c->device));
+  gm_ppo_learner* l = new gm_ppo_learner;
+  l->ctx = c;
+  l->ac = ac;
+  l->opt = o;
+  l->groups = n_groups ? n_groups : GQ_DEFAULT_GROUPS;
+  l->plan_pi = gl_plan(ac->net.actor);
+  l->plan_vf = gl_plan(ac->net.critic);
+  const int rows = std::max(l->plan_pi.total, l->plan_vf.total);
+  l->spill_stride = rows > GL_ARENA ? rows : 1;
+  const size_t total = (size_t)ac->total, G = (size_t)l->groups;
+  hipError_t e = l->d_partials.alloc(total * G);
+  if (e == hipSuccess) e = l->d_wg.alloc(G * GQ_INFO);
+  if (e == hipSuccess) e = l->d_grad.alloc(total);
+  if (e == hipSuccess) e = l->d_m.alloc(total);
+  if (e == hipSuccess) e = l->d_v.alloc(total);
+  if (e == hipSuccess) e = l->d_vmax.alloc(total);
+  if (e == hipSuccess) e = l->d_scalars.alloc(3 * GQ_SCALARS);
+  if (e == hipSuccess) e = l->d_stop.alloc(2);
+  if (e == hipSuccess) e = l->d_spill.alloc((size_t)l->spill_stride * (rows > GL_ARENA ? G : 1));
+  for (float* z : {l->d_grad.get(), l->d_m.get(), l->d_v.get(), l->d_vmax.get()})
+    if (e == hipSuccess) e = hipMemsetAsync(z, 0, sizeof(float) * total, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(l->d_scalars, 0, sizeof(float) * 3 * GQ_SCALARS, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(l->d_stop, 0, sizeof(int32_t) * 2, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    gm_ppo_learner_destroy(l);
+    return fail(c, GM_E_HIP, std::string("gm_ppo_learner_create: ") + hipGetErrorString(e));
+  }
+  *out = l;
+  return GM_OK;
+}
+
+void gm_ppo_learner_destroy(gm_ppo_learner* l) {
+  if (!l) return;
+  if (l->ctx) {
+    (void)hipSetDevice(l->ctx->device);
+    (void)hipStreamSynchronize(l->ctx->stream);   // the stream may still use the learner's buffers
+  }
+  delete l;
+}
+
+int gm_ppo_learner_grad_pi(gm_ppo_learner* l, const gm_ppo_batch* batch) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  if (!ppo_batch_ok(batch, true)) return fail(c, GM_E_ARG, "gm_ppo_learner_grad_pi: incomplete batch (obs, act, logp, adv) or n < 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, ppo_launch_grad(l, true, *batch, nullptr, nullptr, nullptr));
+  return GM_OK;
+}
+
+int gm_ppo_learner_grad_vf(gm_ppo_learner* l, const gm_ppo_batch* batch) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  if (!ppo_batch_ok(batch, false)) return fail(c, GM_E_ARG, "gm_ppo_learner_grad_vf: incomplete batch (obs, ret) or n < 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, ppo_launch_grad(l, false, *batch, nullptr, nullptr, nullptr));
+  return GM_OK;
+}
+
+int gm_ppo_learner_step_pi(gm_ppo_learner* l) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  l->step_pi++;
+  HIPCHK(c, ppo_launch_step(l, true, l->step_pi, nullptr));
+  return GM_OK;
+}
+
+int gm_ppo_learner_step_vf(gm_ppo_learner* l) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  l->step_vf++;
+  HIPCHK(c, ppo_launch_step(l, false, l->step_vf, nullptr));
+  return GM_OK;
+}
+
+int gm_ppo_learner_read(gm_ppo_learner* l, float* grad_flat, float* scalars) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (grad_flat) {
+    const int rc = ac_unpack(c, l->ac, l->d_grad, grad_flat);
+    if (rc != GM_OK) return rc;
+  }
+  return scalars ? read_back(c, scalars, l->d_scalars, sizeof(float) * GQ_SCALARS) : (int)GM_OK;
+}
+
+int gm_ppo_learner_get_state(gm_ppo_learner* l, int64_t* steps, float* exp_avg, float* exp_avg_sq,
+                             float* max_exp_avg_sq) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (steps) { steps[0] = l->step_pi; steps[1] = l->step_vf; }
+  const float* src[3] = {l->d_m, l->d_v, l->d_vmax};
+  float* dst[3] = {exp_avg, exp_avg_sq, max_exp_avg_sq};
+  for (int i = 0; i < 3; i++)
+    if (dst[i]) {
+      const int rc = ac_unpack(c, l->ac, src[i], dst[i]);
+      if (rc != GM_OK) return rc;
+    }
+  return GM_OK;
+}
+
+int gm_ppo_learner_set_state(gm_ppo_learner* l, const int64_t* steps, const float* exp_avg, const float* exp_avg_sq,
+                             const float* max_exp_avg_sq) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  if (steps && (steps[0] < 0 || steps[1] < 0)) return fail(c, GM_E_ARG, "gm_ppo_learner_set_state: negative step");
+  HIPCHK(c, hipSetDevice(c->device));
+  const float* src[3] = {exp_avg, exp_avg_sq, max_exp_avg_sq};
+  float* dst[3] = {l->d_m, l->d_v, l->d_vmax};
+  std::vector<float> packed((size_t)l->ac->total);
+  for (int i = 0; i < 3; i++)
+    if (src[i]) {
+      gq_pack(l->ac->net, l->ac->total, src[i], packed.data());
+      const int rc = stage_upload(c, dst[i], packed.data(), sizeof(float) * packed.size());
+      if (rc != GM_OK) return rc;
+    }
+  if (steps) { l->step_pi = steps[0]; l->step_vf = steps[1]; }
+  return GM_OK;
+}
+
+int gm_ppo_learner_update(gm_ppo_learner* l, const gm_ac_traj* traj, int n_steps, gm_ppo_info* info) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  if (!ac_traj_ok(traj) || n_steps < 1 || n_steps > traj->capacity)
+    return fail(c, GM_E_ARG, "gm_ppo_learner_update: incomplete trajectory buffer or n_steps outside its capacity");
+  const size_t rows = (size_t)n_steps * (size_t)c->n_envs;
+  if (rows < 2) return fail(c, GM_E_ARG, "gm_ppo_learner_update: one row has no standard deviation to normalise with");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (rows > l->rows_cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, l->d_adv.alloc(rows));
+    HIPCHK(c, l->d_ret.alloc(rows));
+    l->rows_cap = rows;
+  }
+  int rc = gm_ac_gae(c, traj, n_steps, (float)l->opt.gamma, (float)l->opt.lam, l->d_adv, l->d_ret);
+  if (rc == GM_OK) rc = gm_ac_adv_normalise(c, l->d_adv, (int64_t)rows);
+  if (rc != GM_OK) return rc;
+  const gm_ppo_batch b{(int64_t)rows, traj->obs, traj->act, traj->logp, l->d_adv, l->d_ret};
+  float* first = l->d_scalars + GQ_SCALARS;
+  float* last = l->d_scalars + 2 * GQ_SCALARS;
+  HIPCHK(c, hipMemsetAsync(l->d_stop, 0, sizeof(int32_t) * 2, c->stream));
+  HIPCHK(c, hipMemsetAsync(first, 0, sizeof(float) * 2 * GQ_SCALARS, c->stream));
+  // the stop latches, so iteration i's step, if taken at all, is optimiser step step_pi + i + 1
+  for (int i = 0; i < l->opt.train_pi_iters; i++) {
+    HIPCHK(c, ppo_launch_grad(l, true, b, l->d_stop, i == 0 ? first : nullptr, last));
+    HIPCHK(c, ppo_launch_step(l, true, l->step_pi + i + 1, l->d_stop));
+  }
+  for (int i = 0; i < l->opt.train_vf_iters; i++) {
+    HIPCHK(c, ppo_launch_grad(l, false, b, nullptr, i == 0 ? first : nullptr, last));
+    HIPCHK(c, ppo_launch_step(l, false, l->step_vf + i + 1, nullptr));
+  }
+  // the one host read: the latch's step count and the info rows
+  struct { int32_t stop[2]; float rows[2 * GQ_SCALARS]; } h;
+  HIPCHK(c, hipMemcpyAsync(h.stop, l->d_stop, sizeof(h.stop), hipMemcpyDeviceToHost, c->stream));
+  rc = read_back(c, h.rows, first, sizeof(h.rows));
+  if (rc != GM_OK) return rc;
+  l->step_pi += h.stop[1];
+  l->step_vf += l->opt.train_vf_iters;
+  if (info) {
+    info->pi_iters_done = h.stop[1];
+    info->pad = 0;
+    std::memcpy(info->first, h.rows, sizeof(float) * GQ_SCALARS);
+    std::memcpy(info->last, h.rows + GQ_SCALARS, sizeof(float) * GQ_SCALARS);
+  }
   return GM_OK;
 }
 

@@ -613,6 +613,8 @@ int64_t gm_struct_size(int which) {
     case 6: return (int64_t)sizeof(gm_spawn_params);
     case 7: return (int64_t)sizeof(gm_calibration);
     case 8: return (int64_t)sizeof(gm_dqn_opt);
+    case 9: return (int64_t)sizeof(gm_ppo_opt);
+    case 10: return (int64_t)sizeof(gm_ppo_info);
     default: return -1;
   }
 }

@@ -95,6 +95,29 @@ __device__ __forceinline__ float gl_soft(float online, float target, float tau) 
   return (float)((double)tau * (double)online + (1.0 - (double)tau) * (double)target);
 }
 
+// the packed layout of a net of these layer sizes: its packed float count, or -1 for more than
+// GP_MAX_LAYERS layers or a width outside 1 .. GP_MAX_WIDTH
+inline int64_t gl_layout(const int32_t* sizes, int n_sizes, GpNet* net) {
+  if (!sizes || n_sizes < 2 || n_sizes - 1 > GP_MAX_LAYERS) return -1;
+  GpNet P{};
+  P.n_layers = n_sizes - 1;
+  long long off = 0;
+  for (int l = 0; l < n_sizes; l++) {
+    if (sizes[l] < 1 || sizes[l] > GP_MAX_WIDTH) return -1;
+    P.width[l] = sizes[l];
+  }
+  for (int l = 0; l < P.n_layers; l++) {
+    P.kpad[l] = (P.width[l] + 3) & ~3;
+    P.tiles[l] = (P.width[l + 1] + 15) / 16;
+    P.woff[l] = off;
+    off += (long long)P.tiles[l] * (P.kpad[l] / 4) * 64;
+    P.boff[l] = off;
+    off += (long long)P.tiles[l] * 16;
+  }
+  if (net) *net = P;
+  return off;
+}
+
 // flat parameter count of a net, and the packed index of flat element i (gm_policy_pack's rule)
 inline int64_t gl_flat_count(const GpNet& P) {
   int64_t n = 0;

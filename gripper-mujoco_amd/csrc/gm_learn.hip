@@ -2,52 +2,31 @@
 // one wave per 16 rows, partial sums per tile) and the elementwise kernel that sums the tiles in
 // order, steps Adam / AdamW and soft-updates a target net (gm_learn_step_kernel).  Shared rules
 // and the row plan are gm_learn.h's; the forward is gm_policy_net.h's chain, kept layer by layer.
+// The layer-wise forward and backward of one tile (gl_forward_rows, gl_backward_rows) and the step
+// kernel are also the PPO learner's (gm_ppo_learn.hip), which passes tanh where this file passes ReLU.
 //
 // Kernels are ordered by the context's stream and, inside a kernel, by workgroup barriers only:
 // no workgroup waits for another one, and no float atomic is used, so two runs give the same bits.
 #pragma once
 #include "gm_learn.h"
 
-// The gradient of mean_i loss(softmax(net(state_i))[action_i] - y_i) over n rows with respect to
-// the packed weights: this tile's 16 rows' share into partials[tile][total] (every entry written,
-// padding entries with 0) and the tile's loss sum into tile_loss[tile].
-//
-// Forward: gp_forward_tile's arithmetic (same MFMA chain, k order, bias placement), every layer's
-// post-activation rows kept -- in LDS when the plan fits GL_ARENA, else in this tile's part of
-// `spill` (global, owned by the learner; written and read by this wave only, between barriers).
-// Backward, per layer l from the last: with D the deltas dL/dz of layer l's outputs (0 in padded
-// columns and in rows >= n) and A the layer's input rows,
-//   dW[j][k] = sum_i D[i][j] A[i][k]   MFMA with M = 16 k's of four k steps, N = 16 j's of a tile,
-//                                       reduction over the batch rows in four chunks of 4; row m
-//                                       of the product stands for k = 4 (s0 + (m & 3)) + (m >> 2),
-//                                       so register r of lane (g, n) is packed element
-//                                       (tile t, k step s0 + r, lane 16 g + n): coalesced stores;
-//   db[j]    = sum_i D[i][j]            in row order;
-//   Dprev[i][k] = [A[i][k] > 0] sum_j D[i][j] W[j][k]   MFMA with M = the 16 rows, N = 16 k's,
-//                                       reduction over j in steps of 4, W gathered from the
-//                                       B-fragment order (4 consecutive floats per (k, j quad)).
-__global__ __launch_bounds__(64) void gm_learn_grad_kernel(const float* __restrict__ state,
-                                                           const int32_t* __restrict__ action,
-                                                           const float* __restrict__ y, int n,
-                                                           const float* __restrict__ params, GpNet P, GlPlan L,
-                                                           int loss_kind, float* __restrict__ spill,
-                                                           float* __restrict__ partials, long long total,
-                                                           float* __restrict__ tile_loss) {
-  __shared__ float arena[GL_ARENA];
-  __shared__ float row_loss[GP_TILE];
-  const int lane = threadIdx.x;
-  const int g = lane >> 4, nn = lane & 15;
-  const int e0 = blockIdx.x * GP_TILE;
-  float* base = L.total <= GL_ARENA ? arena : spill + (size_t)blockIdx.x * L.total;
-  float* part = partials + (size_t)blockIdx.x * total;
+#define GL_AHEAD 8   // k steps whose operands gl_forward_rows / gl_backward_rows load ahead of the MFMA chain
 
-  // ---- forward, every layer's rows kept
+// One tile's forward with every layer's rows kept: gp_forward_tile's arithmetic (same MFMA chain,
+// k order, bias placement; hidden layers through gp_activate(code), a caller's literal) on rows
+// e0 .. e0 + 15 of x[n][width 0], the post-activation rows of every layer left under the plan L
+// from `base` -- LDS when the plan fits GL_ARENA, else the caller's global spill rows (written
+// and read by this wave only, between barriers).  Rows >= n and padded columns are 0.
+__device__ __forceinline__ void gl_forward_rows(const float* __restrict__ x, size_t e0, size_t n,
+                                                const float* __restrict__ params, const GpNet& P, const GlPlan& L,
+                                                float* base, int code, int lane) {
+  const int g = lane >> 4, nn = lane & 15;
   {
     const int n_obs = P.width[0], k0 = P.kpad[0], S0 = L.a_stride[0];
     float* A0 = base + L.a_off[0];
     for (int i = lane; i < GP_TILE * k0; i += 64) {
       const int r = i / k0, k = i - r * k0;
-      A0[r * S0 + k] = (e0 + r < n && k < n_obs) ? state[(size_t)(e0 + r) * n_obs + k] : 0.0f;
+      A0[r * S0 + k] = (e0 + r < n && k < n_obs) ? x[(e0 + r) * n_obs + k] : 0.0f;
     }
   }
   __syncthreads();
@@ -63,28 +42,150 @@ __global__ __launch_bounds__(64) void gm_learn_grad_kernel(const float* __restri
     for (int t = 0; t < P.tiles[l]; t++) {
       gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
       const float* Wt = W + (size_t)t * ksteps * 64;
-      for (int s = 0; s < ksteps; s++) {
-        const float a = in[nn * Si + 4 * s + g];
-        const float b = Wt[s * 64 + lane];
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+      // GL_AHEAD k steps' operands are loaded ahead of their MFMAs (one wait for the loads of W
+      // where one per MFMA would serialise the chain on L2's latency); the MFMAs keep their k order
+      for (int s0 = 0; s0 < ksteps; s0 += GL_AHEAD) {
+        const int m = min(GL_AHEAD, ksteps - s0);
+        float a[GL_AHEAD], b[GL_AHEAD];
+#pragma unroll
+        for (int u = 0; u < GL_AHEAD; u++) {
+          a[u] = u < m ? in[nn * Si + 4 * (s0 + u) + g] : 0.0f;
+          b[u] = u < m ? Wt[(s0 + u) * 64 + lane] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < GL_AHEAD; u++)
+          if (u < m) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u], c, 0, 0, 0);
       }
       const int j = t * 16 + nn;
       const float bias = Bv[j];
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         float v = c[r] + bias;
-        if (!last) v = gp_activate(v, GP_ACT_RELU);
+        if (!last) v = gp_activate(v, code);
         out[(g * 4 + r) * So + j] = (j < outw) ? v : 0.0f;
       }
     }
     __syncthreads();
   }
+}
+
+// dL/dz of a hidden layer from dL/da (c) and the stored activation a: ReLU's [a > 0], tanh's 1 - a^2
+__device__ __forceinline__ float gl_act_grad(float c, float a, int code) {
+  return code == GP_ACT_TANH ? c * (1.0f - a * a) : (a > 0.0f ? c : 0.0f);
+}
+
+// One tile's backward through the layers, from the deltas of the last layer's outputs in the
+// plan's delta rows 0 (0 in padded columns and in rows >= n): this tile's share of the gradient
+// with respect to the packed weights into part[net's packed count] -- every entry written,
+// padding entries with 0; with `add`, added to what part holds (a workgroup's running sum over
+// its tiles: each entry is read and written by the same lane every time).  Per layer l from the
+// last, with D the deltas dL/dz of layer l's outputs and A the layer's input rows,
+//   dW[j][k] = sum_i D[i][j] A[i][k]   MFMA with M = 16 k's of four k steps, N = 16 j's of a tile,
+//                                       reduction over the batch rows in four chunks of 4; row m
+//                                       of the product stands for k = 4 (s0 + (m & 3)) + (m >> 2),
+//                                       so register r of lane (g, n) is packed element
+//                                       (tile t, k step s0 + r, lane 16 g + n): coalesced stores;
+//   db[j]    = sum_i D[i][j]            in row order;
+//   Dprev[i][k] = act'(A[i][k]) sum_j D[i][j] W[j][k]   MFMA with M = the 16 rows, N = 16 k's,
+//                                       reduction over j in steps of 4, W gathered from the
+//                                       B-fragment order (4 consecutive floats per (k, j quad)).
+__device__ __forceinline__ void gl_backward_rows(const float* __restrict__ params, const GpNet& P, const GlPlan& L,
+                                                 float* base, float* __restrict__ part, int code, bool add, int lane) {
+  const int g = lane >> 4, nn = lane & 15;
+  const int nl = P.n_layers;
+  const int Sd = L.d_stride;
+  int cur = 0;
+  for (int l = nl - 1; l >= 0; l--) {
+    const float* __restrict__ W = params + P.woff[l];
+    const int kpad = P.kpad[l], ksteps = kpad >> 2;
+    const float* A = base + L.a_off[l];
+    const int Sa = L.a_stride[l];
+    const float* D = base + L.d_off[cur];
+    // dW in packed order
+    const int km = 4 * (nn & 3) + (nn >> 2);       // the k (within 16) that product row m = nn stands for
+    for (int t = 0; t < P.tiles[l]; t++)
+      for (int s0 = 0; s0 < ksteps; s0 += 4) {
+        gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+        const int k = 4 * s0 + km;
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) {
+          const int i = 4 * ch + g;
+          const float a = k < kpad ? A[i * Sa + k] : 0.0f;
+          const float b = D[i * Sd + 16 * t + nn];
+          c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          if (s0 + r < ksteps) {
+            float* q = part + P.woff[l] + ((long long)t * ksteps + s0 + r) * 64 + lane;
+            *q = add ? *q + c[r] : c[r];
+          }
+      }
+    // db
+    for (int j = lane; j < P.tiles[l] * 16; j += 64) {
+      float s = 0.0f;
+      for (int i = 0; i < GP_TILE; i++) s += D[i * Sd + j];
+      float* q = part + P.boff[l] + j;
+      *q = add ? *q + s : s;
+    }
+    if (l == 0) break;
+    // the deltas of the layer below, through W and the activation that made A
+    float* Dn = base + L.d_off[cur ^ 1];
+    const int wprev = P.tiles[l - 1] * 16;
+    const int jmax = (P.width[l + 1] + 3) & ~3;    // (the deltas of padded columns are 0)
+    for (int kb = 0; kb < wprev; kb += 16) {
+      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+      const int k = kb + nn;
+      for (int q0 = 0; q0 < jmax; q0 += 4 * GL_AHEAD) {     // (operands ahead of their MFMAs, as in the forward)
+        const int m = min(GL_AHEAD, (jmax - q0) >> 2);
+        float a[GL_AHEAD], b[GL_AHEAD];
+#pragma unroll
+        for (int u = 0; u < GL_AHEAD; u++) {
+          const int j = q0 + 4 * u + g;
+          a[u] = u < m ? D[nn * Sd + j] : 0.0f;
+          b[u] = (u < m && k < kpad) ? W[((size_t)(j >> 4) * ksteps + (k >> 2)) * 64 + (k & 3) * 16 + (j & 15)] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < GL_AHEAD; u++)
+          if (u < m) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u], c, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int i = 4 * g + r;
+        Dn[i * Sd + k] = gl_act_grad(c[r], A[i * Sa + k], code);
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+
+// The gradient of mean_i loss(softmax(net(state_i))[action_i] - y_i) over n rows with respect to
+// the packed weights: this tile's 16 rows' share into partials[tile][total] (every entry written,
+// padding entries with 0) and the tile's loss sum into tile_loss[tile].  Forward and backward are
+// gl_forward_rows and gl_backward_rows with ReLU as a literal (the PPO learner's kernels,
+// gm_ppo_learn.hip, call the same two with tanh); rows in LDS when the plan fits GL_ARENA, else
+// in this tile's part of `spill` (global, owned by the learner).
+__global__ __launch_bounds__(64) void gm_learn_grad_kernel(const float* __restrict__ state,
+                                                           const int32_t* __restrict__ action,
+                                                           const float* __restrict__ y, int n,
+                                                           const float* __restrict__ params, GpNet P, GlPlan L,
+                                                           int loss_kind, float* __restrict__ spill,
+                                                           float* __restrict__ partials, long long total,
+                                                           float* __restrict__ tile_loss) {
+  __shared__ float arena[GL_ARENA];
+  __shared__ float row_loss[GP_TILE];
+  const int lane = threadIdx.x;
+  const int e0 = blockIdx.x * GP_TILE;
+  float* base = L.total <= GL_ARENA ? arena : spill + (size_t)blockIdx.x * L.total;
+  float* part = partials + (size_t)blockIdx.x * total;
+
+  gl_forward_rows(state, (size_t)e0, (size_t)n, params, P, L, base, GP_ACT_RELU, lane);
 
   // ---- loss and the deltas of the logits: one lane per row
   const int nl = P.n_layers;
   const int n_out = P.width[nl];
   const int Sd = L.d_stride;
-  int cur = 0;
   {
     float* D = base + L.d_off[0];
     const int wd = P.tiles[nl - 1] * 16;
@@ -122,59 +223,7 @@ __global__ __launch_bounds__(64) void gm_learn_grad_kernel(const float* __restri
     tile_loss[blockIdx.x] = s;
   }
 
-  // ---- backward
-  for (int l = nl - 1; l >= 0; l--) {
-    const float* __restrict__ W = params + P.woff[l];
-    const int kpad = P.kpad[l], ksteps = kpad >> 2;
-    const float* A = base + L.a_off[l];
-    const int Sa = L.a_stride[l];
-    const float* D = base + L.d_off[cur];
-    // dW in packed order
-    const int km = 4 * (nn & 3) + (nn >> 2);       // the k (within 16) that product row m = nn stands for
-    for (int t = 0; t < P.tiles[l]; t++)
-      for (int s0 = 0; s0 < ksteps; s0 += 4) {
-        gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
-        const int k = 4 * s0 + km;
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++) {
-          const int i = 4 * ch + g;
-          const float a = k < kpad ? A[i * Sa + k] : 0.0f;
-          const float b = D[i * Sd + 16 * t + nn];
-          c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-          if (s0 + r < ksteps) part[P.woff[l] + ((long long)t * ksteps + s0 + r) * 64 + lane] = c[r];
-      }
-    // db
-    for (int j = lane; j < P.tiles[l] * 16; j += 64) {
-      float s = 0.0f;
-      for (int i = 0; i < GP_TILE; i++) s += D[i * Sd + j];
-      part[P.boff[l] + j] = s;
-    }
-    if (l == 0) break;
-    // the deltas of the layer below, through W and the ReLU that made A
-    float* Dn = base + L.d_off[cur ^ 1];
-    const int wprev = P.tiles[l - 1] * 16;
-    const int jmax = (P.width[l + 1] + 3) & ~3;    // (the deltas of padded columns are 0)
-    for (int kb = 0; kb < wprev; kb += 16) {
-      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
-      const int k = kb + nn;
-      for (int j0 = 0; j0 < jmax; j0 += 4) {
-        const int j = j0 + g;
-        const float a = D[nn * Sd + j];
-        const float b = k < kpad ? W[((size_t)(j >> 4) * ksteps + (k >> 2)) * 64 + (k & 3) * 16 + (j & 15)] : 0.0f;
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int i = 4 * g + r;
-        Dn[i * Sd + k] = A[i * Sa + k] > 0.0f ? c[r] : 0.0f;
-      }
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
+  gl_backward_rows(params, P, L, base, part, GP_ACT_RELU, false, lane);
 }
 
 // what one launch of gm_learn_step_kernel does, in this order, per packed element
@@ -196,11 +245,15 @@ struct GlStepArgs {
   float* target;
   float tau;
   GlOpt opt;
+  const int* skip;       // NULL, or a device flag: nonzero makes the launch a no-op (the PPO learner's KL stop)
+  long long gap_at, gap_len;   // element i >= gap_at lies gap_len further on (0: none; the PPO blob's
+                               // [actor | critic | log_std], whose policy optimiser skips the critic)
 };
 
 __global__ __launch_bounds__(256) void gm_learn_step_kernel(GlStepArgs a) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.total) return;
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.total || (a.skip && *a.skip)) return;
+  if (a.gap_len != 0 && i >= a.gap_at) i += a.gap_len;   // (never with do_sum: the partials have no gap)
   float g = 0.0f;
   if (a.do_sum) {
     for (int t = 0; t < a.n_tiles; t++) g += a.partials[(size_t)t * a.total + i];

@@ -156,6 +156,30 @@ class DqnOpt(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class PpoOpt(C.Structure):
+    """gm_ppo_opt (include/gripper_mi355x.h): Agent_PPO.Parameters' learner options."""
+    _fields_ = [("learning_rate_pi", C.c_double), ("learning_rate_vf", C.c_double), ("gamma", C.c_double),
+                ("lam", C.c_double), ("clip_ratio", C.c_double), ("train_pi_iters", C.c_int32),
+                ("train_vf_iters", C.c_int32), ("target_kl", C.c_double), ("max_kl_ratio", C.c_double),
+                ("optimiser", C.c_int32), ("use_kl_penalty", C.c_int32), ("kl_penalty_coefficient", C.c_double),
+                ("use_entropy_regularisation", C.c_int32), ("pad", C.c_int32), ("entropy_coefficient", C.c_double),
+                ("adam_beta1", C.c_double), ("adam_beta2", C.c_double), ("grad_clamp_value", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class PpoBatch(C.Structure):
+    """gm_ppo_batch: n rows of device arrays."""
+    _fields_ = [("n", C.c_int64), ("obs", C.c_void_p), ("act", C.c_void_p), ("logp", C.c_void_p),
+                ("adv", C.c_void_p), ("ret", C.c_void_p)]
+
+
+class PpoInfo(C.Structure):
+    """gm_ppo_info: what one gm_ppo_learner_update did."""
+    _fields_ = [("pi_iters_done", C.c_int32), ("pad", C.c_int32), ("first", C.c_float * 5), ("last", C.c_float * 5)]
+
+
 OPT_ADAM, OPT_ADAMW = 0, 1
 LOSS_SMOOTH_L1, LOSS_MSE = 0, 1
 
@@ -208,7 +232,8 @@ def load_library(path: str | None = None):
             "(run `python -c 'import __graft_entry__ as g; g.build()'` from the repo root)")
     lib = C.CDLL(p)
     _declare(lib)
-    sizes = {0: Settings, 3: Object, 4: Spawn, 5: ModelParams, 6: SpawnParams, 7: Calibration, 8: DqnOpt}
+    sizes = {0: Settings, 3: Object, 4: Spawn, 5: ModelParams, 6: SpawnParams, 7: Calibration, 8: DqnOpt, 9: PpoOpt,
+             10: PpoInfo}
     for which, cls in sizes.items():
         n = lib.gm_struct_size(which)
         if n < 0 and os.environ.get("GM_LIB"):
@@ -324,6 +349,20 @@ def _declare(lib):
         "gm_ac_finish": (i32, [vp, vp, i32]),
         "gm_ac_rollout": (i32, [vp, vp, i32, i32, C.c_float, C.c_uint64, C.c_uint64, i32, vp]),
         "gm_ac_gae": (i32, [vp, vp, i32, C.c_float, C.c_float, vp, vp]),
+        "gm_ac_adv_normalise": (i32, [vp, vp, C.c_int64]),
+        "gm_ac_get_params": (i32, [vp, f32p]),
+        "gm_ac_get_packed": (i32, [vp, f32p]),
+        "gm_ppo_opt_default": (None, [vp]),
+        "gm_ppo_learner_create": (i32, [vp, vp, i32, C.POINTER(vp)]),
+        "gm_ppo_learner_destroy": (None, [vp]),
+        "gm_ppo_learner_grad_pi": (i32, [vp, vp]),
+        "gm_ppo_learner_grad_vf": (i32, [vp, vp]),
+        "gm_ppo_learner_step_pi": (i32, [vp]),
+        "gm_ppo_learner_step_vf": (i32, [vp]),
+        "gm_ppo_learner_read": (i32, [vp, f32p, f32p]),
+        "gm_ppo_learner_get_state": (i32, [vp, C.POINTER(C.c_int64), f32p, f32p, f32p]),
+        "gm_ppo_learner_set_state": (i32, [vp, C.POINTER(C.c_int64), f32p, f32p, f32p]),
+        "gm_ppo_learner_update": (i32, [vp, vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -7,9 +7,10 @@ Mirrors the reference's policy-gradient rollout side:
     mlp([...], Tanh) with an identity output layer (:47-55, 449-500);
   - Agent_PPO.select_action (:1348-1388): uniform exploration noise added after logp;
   - PPOBuffer (:301-409): finish_trajectory's GAE-lambda advantages and rewards-to-go, get()'s
-    advantage normalisation.
-There is no trainer here: the learner is the user's torch code, which reads
-TrajectoryBuffer.get() and hands new weights back with DeviceActorCritic.set_params().
+    advantage normalisation;
+and its learner, Agent_PPO.optimise_model (:1440-1522): DevicePPOLearner runs compute_loss_pi's
+and compute_loss_v's backward, both Adam / AdamW optimisers and the KL stop on the device weights
+the rollout reads, so a training loop is ac.rollout(traj) followed by learner.update(traj).
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import load_library
+from ._lib import load_library, PpoOpt, PpoBatch, PpoInfo, OPT_ADAM, OPT_ADAMW
 from .policy import _M64, _mix, as_f32, linear_init, state_dict_net
 
 DEFAULT_HIDDEN = (64, 64)          # MLPActorCriticPG's default hidden_sizes
@@ -162,6 +163,21 @@ class TrajectoryBuffer:
                     ret=ret.reshape(-1), adv=((adv - mean) / std).reshape(-1), logp=self.logp[:k].reshape(-1))
 
 
+def adv_normalise(env, adv):
+    """gm_ac_adv_normalise in place on a contiguous float32 device tensor: adv <- (adv - mean) /
+    std with torch.std_mean's unbiased std (PPOBuffer.get), the sums in double in a fixed order.
+    Returns adv.  One element raises: its standard deviation is undefined."""
+    import torch
+    if adv.dtype != torch.float32 or not adv.is_cuda or not adv.is_contiguous():
+        raise ValueError("a contiguous float32 device tensor expected")
+    torch.cuda.synchronize(adv.device)     # torch-side writes to adv
+    rc = env.lib.gm_ac_adv_normalise(env.ctx, C.c_void_p(adv.data_ptr()), int(adv.numel()))
+    if rc != 0:
+        raise RuntimeError(env.lib.gm_last_error(env.ctx).decode() or f"gm_ac_adv_normalise failed ({rc})")
+    torch.cuda.synchronize(adv.device)     # the env's stream, before torch reads the result
+    return adv
+
+
 class DeviceActorCritic:
     """An MLPActorCriticPG (Gaussian actor, critic) bound to a BatchedGripperEnv with
     continuous actions."""
@@ -173,6 +189,8 @@ class DeviceActorCritic:
         hv = hidden if hidden_v is None else hidden_v
         self.actor_sizes = [int(x) for x in (actor_sizes or [env.n_obs, *hidden, env.n_actions])]
         self.critic_sizes = [int(x) for x in (critic_sizes or [env.n_obs, *hv, 1])]
+        #: the last weights handed in from the host (the constructor's, set_params'); a
+        #: DevicePPOLearner's steps do not reach it: get_params() returns the device's
         self.params = (init_params(self.actor_sizes, self.critic_sizes, seed) if params is None
                        else np.ascontiguousarray(params, np.float32).copy())
         self._p = C.c_void_p()
@@ -204,6 +222,34 @@ class DeviceActorCritic:
             raise ValueError(f"{self.params.size} parameters expected, got {p.size}")
         self.params = p.copy()
         self._check(self.lib.gm_ac_set_params(self._p, self.params.ctypes.data_as(C.POINTER(C.c_float))), "gm_ac_set_params")
+
+    def get_params(self) -> np.ndarray:
+        """The device's weights in init_params' flat order (the inverse of set_params), as a
+        DevicePPOLearner's steps left them.  self.params keeps the last weights handed in."""
+        out = np.empty(self.params.size, dtype=np.float32)
+        self._check(self.lib.gm_ac_get_params(self._p, out.ctypes.data_as(C.POINTER(C.c_float))), "gm_ac_get_params")
+        return out
+
+    def get_packed(self) -> np.ndarray:
+        """The device's weights as stored (pack()'s layout, padding entries included)."""
+        out = np.empty(pack(self.actor_sizes, self.critic_sizes, self.params)[0].size, dtype=np.float32)
+        self._check(self.lib.gm_ac_get_packed(self._p, out.ctypes.data_as(C.POINTER(C.c_float))), "gm_ac_get_packed")
+        return out
+
+    def state_dict(self) -> dict:
+        """The device's weights under MLPActorCriticPG's key names (pi.log_std, pi.mu_net.{0,2,..}
+        .weight / .bias, vf.v_net.{0,2,..}.weight / .bias) as numpy arrays: what
+        params_from_state_dict and set_params read."""
+        flat, pos, out = self.get_params(), 0, {}
+        for prefix, sizes in (("pi.mu_net.", self.actor_sizes), ("vf.v_net.", self.critic_sizes)):
+            for l in range(len(sizes) - 1):
+                fin, fout = sizes[l], sizes[l + 1]
+                out[f"{prefix}{2 * l}.weight"] = flat[pos:pos + fout * fin].reshape(fout, fin).copy()
+                pos += fout * fin
+                out[f"{prefix}{2 * l}.bias"] = flat[pos:pos + fout].copy()
+                pos += fout
+        out["pi.log_std"] = flat[pos:].copy()
+        return out
 
     def act(self, traj: TrajectoryBuffer, k: int, sample: bool = True, noise: float = 0.0, seed: int = 0,
             decision: int = 0):
@@ -243,6 +289,168 @@ class DeviceActorCritic:
         if self._p:
             self.lib.gm_ac_destroy(self._p)
             self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_OPTIMISERS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW}
+# Agent_PPO.Parameters' learner options (PolicyGradient.py:1196-1220) and their defaults
+PPO_DEFAULTS = dict(learning_rate_pi=3e-4, learning_rate_vf=1e-3, gamma=0.99, clip_ratio=0.2, train_pi_iters=80,
+                    train_vf_iters=80, lam=0.97, target_kl=0.01, max_kl_ratio=1.5, optimiser="adam",
+                    use_kl_penalty=False, use_entropy_regularisation=False, kl_penalty_coefficient=0.2,
+                    entropy_coefficient=1e-4, adam_beta1=0.9, adam_beta2=0.999, grad_clamp_value=None)
+
+
+def ppo_opt(**options) -> PpoOpt:
+    """Agent_PPO.Parameters' learner options under their own names (PPO_DEFAULTS) as a gm_ppo_opt:
+    "adam" is torch.optim.Adam(lr, betas), "adamW" torch.optim.AdamW(lr, betas, amsgrad=True), as
+    Agent_PPO.init builds them; grad_clamp_value None disables the clamp.  Unknown names raise, as
+    Parameters.update does.  No GPU needed."""
+    unknown = sorted(set(options) - set(PPO_DEFAULTS))
+    if unknown:
+        raise ValueError(f"incorrect key: {', '.join(unknown)}")
+    v = dict(PPO_DEFAULTS, **options)
+    name = str(v["optimiser"]).lower()
+    if name not in _OPTIMISERS:
+        raise ValueError(f"optimiser {v['optimiser']!r}: 'adam' or 'adamW' expected (RMSprop is not on the device)")
+    o = PpoOpt()
+    for k in ("learning_rate_pi", "learning_rate_vf", "gamma", "lam", "clip_ratio", "target_kl", "max_kl_ratio",
+              "kl_penalty_coefficient", "entropy_coefficient", "adam_beta1", "adam_beta2"):
+        setattr(o, k, float(v[k]))
+    o.train_pi_iters, o.train_vf_iters = int(v["train_pi_iters"]), int(v["train_vf_iters"])
+    o.optimiser = _OPTIMISERS[name]
+    o.use_kl_penalty, o.use_entropy_regularisation = int(bool(v["use_kl_penalty"])), int(bool(v["use_entropy_regularisation"]))
+    o.grad_clamp_value = 0.0 if v["grad_clamp_value"] is None else float(v["grad_clamp_value"])
+    return o
+
+
+def ppo_opt_default() -> PpoOpt:
+    """gm_ppo_opt_default: the library's own defaults (equal to ppo_opt()'s)."""
+    o = PpoOpt()
+    load_library().gm_ppo_opt_default(C.byref(o))
+    return o
+
+
+SCALARS = ("loss_pi", "loss_v", "kl", "ent", "cf")      # gm_ppo_learner_read's order
+
+
+class DevicePPOLearner:
+    """Agent_PPO.optimise_model on the device weights of `ac`: compute_loss_pi's and
+    compute_loss_v's backward, pi_optimiser (actor net and log_std) and vf_optimiser (critic), the
+    KL stop.  Options are Agent_PPO.Parameters' names (ppo_opt); n_groups: workgroups per gradient
+    launch (None: the library's default) -- results are bit for bit reproducible for one n_groups."""
+
+    def __init__(self, ac: DeviceActorCritic, n_groups: int | None = None, **options):
+        self.ac, self.env, self.lib = ac, ac.env, ac.lib
+        self.opt = ppo_opt(**options)
+        self._l = C.c_void_p()
+        self._check(self.lib.gm_ppo_learner_create(ac._p, C.byref(self.opt), int(n_groups or 0), C.byref(self._l)),
+                    "gm_ppo_learner_create")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(self.lib.gm_last_error(self.env.ctx).decode() or f"{what} failed ({rc})")
+
+    def _handle(self):
+        if not self._l:
+            raise RuntimeError("the learner is closed")
+        return self._l
+
+    def _batch(self, data: dict, keys) -> PpoBatch:
+        """The gm_ppo_batch of TrajectoryBuffer.get()'s dict (or any dict of contiguous f32 device
+        tensors under those keys); the tensors named in `keys` are checked and passed."""
+        import torch
+        n = int(data["obs"].shape[0])
+        want = dict(obs=(n, self.env.n_obs), act=(n, self.env.n_actions), logp=(n,), adv=(n,), ret=(n,))
+        b = PpoBatch()
+        b.n = n
+        for k in keys:
+            t = data[k]
+            if tuple(t.shape) != want[k] or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{k}: a contiguous float32 device tensor of shape {want[k]} expected, "
+                                 f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+            setattr(b, k, t.data_ptr())
+        return b
+
+    def _grad(self, fn, name, data, keys):
+        import torch
+        h = self._handle()
+        b = self._batch(data, keys)
+        dev = data["obs"].device
+        torch.cuda.synchronize(dev)     # torch-side writes to the batch
+        self._check(fn(h, C.byref(b)), name)
+        torch.cuda.synchronize(dev)     # the env's stream, before torch reuses the tensors
+
+    def grad_pi(self, data: dict):
+        """compute_loss_pi(data).backward(): leaves the policy's raw gradient, loss_pi, kl, ent, cf."""
+        self._grad(self.lib.gm_ppo_learner_grad_pi, "gm_ppo_learner_grad_pi", data, ("obs", "act", "logp", "adv"))
+
+    def grad_vf(self, data: dict):
+        """compute_loss_v(data).backward(): leaves the critic's raw gradient and loss_v."""
+        self._grad(self.lib.gm_ppo_learner_grad_vf, "gm_ppo_learner_grad_vf", data, ("obs", "ret"))
+
+    def step_pi(self):
+        """clip_grad_value_ and pi_optimiser.step() on the held gradient, in place on the actor and log_std."""
+        self._check(self.lib.gm_ppo_learner_step_pi(self._handle()), "gm_ppo_learner_step_pi")
+
+    def step_vf(self):
+        """clip_grad_value_ and vf_optimiser.step() on the held gradient, in place on the critic."""
+        self._check(self.lib.gm_ppo_learner_step_vf(self._handle()), "gm_ppo_learner_step_vf")
+
+    def read(self):
+        """(held gradient in init_params' flat order, dict of loss_pi, loss_v, kl, ent, cf as float32)."""
+        g = np.empty(self.ac.params.size, dtype=np.float32)
+        sc = np.empty(len(SCALARS), dtype=np.float32)
+        f32p = C.POINTER(C.c_float)
+        self._check(self.lib.gm_ppo_learner_read(self._handle(), g.ctypes.data_as(f32p), sc.ctypes.data_as(f32p)),
+                    "gm_ppo_learner_read")
+        return g, dict(zip(SCALARS, sc))
+
+    def state(self) -> dict:
+        """Both optimisers' state in flat order (the policy's entries pi_optimiser's, the critic's
+        vf_optimiser's): step_pi, step_vf, exp_avg, exp_avg_sq, max_exp_avg_sq."""
+        f32p = C.POINTER(C.c_float)
+        n = self.ac.params.size
+        steps = (C.c_int64 * 2)()
+        out = {k: np.empty(n, dtype=np.float32) for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")}
+        self._check(self.lib.gm_ppo_learner_get_state(self._handle(), steps, *(out[k].ctypes.data_as(f32p) for k in out)),
+                    "gm_ppo_learner_get_state")
+        return dict(step_pi=int(steps[0]), step_vf=int(steps[1]), **out)
+
+    def load_state(self, state: dict):
+        f32p = C.POINTER(C.c_float)
+        n = self.ac.params.size
+        arrs = [np.ascontiguousarray(as_f32(state[k]), np.float32).ravel()
+                for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")]
+        if any(a.size != n for a in arrs):
+            raise ValueError(f"{n} entries per moment expected")
+        steps = (C.c_int64 * 2)(int(state["step_pi"]), int(state["step_vf"]))
+        self._check(self.lib.gm_ppo_learner_set_state(self._handle(), steps, *(a.ctypes.data_as(f32p) for a in arrs)),
+                    "gm_ppo_learner_set_state")
+
+    def update(self, traj: TrajectoryBuffer, n_steps: int | None = None) -> dict:
+        """optimise_model on the first n_steps rows of traj (default: all), enqueued with one host
+        read at the end: GAE -> advantage normalisation -> the policy loop with its KL stop -> the
+        value loop.  Returns pi_iters_done and the first and last loss_pi, loss_v, kl, ent, cf."""
+        import torch
+        h = self._handle()
+        k = traj.K if n_steps is None else int(n_steps)
+        t = traj.struct()
+        info = PpoInfo()
+        torch.cuda.synchronize(traj.obs.device)     # torch-side writes to the buffers (tests)
+        self._check(self.lib.gm_ppo_learner_update(h, C.byref(t), k, C.byref(info)), "gm_ppo_learner_update")
+        return dict(pi_iters_done=int(info.pi_iters_done),
+                    first=dict(zip(SCALARS, np.array(info.first[:], dtype=np.float32))),
+                    last=dict(zip(SCALARS, np.array(info.last[:], dtype=np.float32))))
+
+    def close(self):
+        if self._l:
+            self.lib.gm_ppo_learner_destroy(self._l)
+            self._l = C.c_void_p()
 
     def __del__(self):
         try:

@@ -912,6 +912,93 @@ int  gm_ac_rollout(gm_ac* p, const gm_ac_traj* traj, int n_steps, int sample, fl
  * boot, last_val only); adv, ret: device [n_steps][n_envs]. */
 int  gm_ac_gae(gm_ctx* ctx, const gm_ac_traj* traj, int n_steps, float gamma, float lam, float* adv,
                float* ret);
+/* PPOBuffer.get's advantage normalisation (PolicyGradient.py:384-407) in place on a device array:
+ * adv <- (adv - mean) / std, std the unbiased standard deviation as torch.std_mean gives it.  The
+ * sums are formed in double in a fixed order: the same input gives the same bytes.  n < 2 is
+ * GM_E_ARG (the standard deviation of one value is undefined). */
+int  gm_ac_adv_normalise(gm_ctx* ctx, float* adv, int64_t n);
+/* The inverse of gm_ac_set_params: the device weights in gm_ac_create's flat order (host pointer). */
+int  gm_ac_get_params(gm_ac* p, float* flat);
+/* The device weights as stored, gm_ac_pack's layout and count (host pointer): the padding entries
+ * included, which must stay exactly 0 under every update. */
+int  gm_ac_get_packed(gm_ac* p, float* packed);
+
+/* ---- PPO learner: clipped-surrogate backward, two Adams, KL stop ----
+ * Agent_PPO.optimise_model (rl/agents/PolicyGradient.py:1440-1522) on the packed weights where the
+ * rollout reads them: gradients and moments live in gm_ac_pack's layout, the steps update the
+ * actor-critic in place, nothing is repacked and no weight crosses the bus.  f32; no float atomics:
+ * the same call on the same inputs with the same n_groups gives the same bits.  Full-batch like the
+ * reference; RMSprop is not here. */
+typedef struct gm_ppo_opt {     /* Agent_PPO.Parameters' learner options (PolicyGradient.py:1196-1220);
+                                   doubles, as torch keeps its hyperparameters */
+  double  learning_rate_pi, learning_rate_vf, gamma, lam, clip_ratio;
+  int32_t train_pi_iters, train_vf_iters;
+  double  target_kl, max_kl_ratio;
+  int32_t optimiser;            /* GM_OPT_ADAM: Adam(lr, betas); GM_OPT_ADAMW: AdamW(lr, betas, amsgrad=True),
+                                   weight_decay 0.01 (torch's default), as Agent_PPO.init passes them */
+  int32_t use_kl_penalty;
+  double  kl_penalty_coefficient;
+  int32_t use_entropy_regularisation;
+  int32_t pad;
+  double  entropy_coefficient, adam_beta1, adam_beta2;
+  double  grad_clamp_value;     /* clip_grad_value_'s bound; <= 0: none (Parameters' None) */
+} gm_ppo_opt;
+/* Parameters' defaults: lr 3e-4 / 1e-3, gamma 0.99, lam 0.97, clip 0.2, 80 + 80 iterations,
+ * target_kl 0.01, max_kl_ratio 1.5, Adam, no KL penalty (0.2), no entropy term (1e-4), betas
+ * (0.9, 0.999), no clamp */
+void gm_ppo_opt_default(gm_ppo_opt* out);
+/* n rows of a batch, device arrays: the first k rows of a trajectory buffer are already in this
+ * shape ([k * n_envs] rows). */
+typedef struct gm_ppo_batch {
+  int64_t n;
+  const float* obs;             /* [n][n_obs] */
+  const float* act;             /* [n][n_actions] */
+  const float* logp;            /* [n]  log-probabilities under the policy that collected the rows */
+  const float* adv;             /* [n]  (normalised) advantages */
+  const float* ret;             /* [n]  rewards-to-go */
+} gm_ppo_batch;
+typedef struct gm_ppo_info {    /* what one gm_ppo_learner_update did */
+  int32_t pi_iters_done;        /* policy iterations that stepped (the KL stop ends them early) */
+  int32_t pad;
+  float   first[5], last[5];    /* loss_pi, loss_v, kl, ent, cf of the first and of the last iteration
+                                   evaluated (policy: the one that stopped, when one did) */
+} gm_ppo_info;
+/* A learner for `ac`, on its context, with n_groups workgroups per gradient launch (0: the default;
+ * its buffers depend on n_groups and the net, never on the batch): owns one partial gradient per
+ * workgroup, the summed gradient, both optimisers' exp_avg / exp_avg_sq / max_exp_avg_sq (zero)
+ * and step counts (0).  GM_E_ARG with a gm_last_error text for an optimiser other than
+ * GM_OPT_ADAM / GM_OPT_ADAMW (RMSprop is not on the device).  Destroy it before `ac`. */
+typedef struct gm_ppo_learner gm_ppo_learner;
+int  gm_ppo_learner_create(gm_ac* ac, const gm_ppo_opt* opt, int n_groups, gm_ppo_learner** out);
+void gm_ppo_learner_destroy(gm_ppo_learner* l);
+/* compute_loss_pi's backward (reads obs, act, logp, adv) and compute_loss_v's (reads obs, ret) for
+ * the batch: leave the raw gradient of the policy's parameters (actor net, log_std) / the critic's
+ * and loss_pi, kl, ent, cf / loss_v on the device.  n < 1 or a missing array is GM_E_ARG. */
+int  gm_ppo_learner_grad_pi(gm_ppo_learner* l, const gm_ppo_batch* batch);
+int  gm_ppo_learner_grad_vf(gm_ppo_learner* l, const gm_ppo_batch* batch);
+/* clip_grad_value_ and pi_optimiser.step() / vf_optimiser.step() on the held gradient, in place on
+ * the device weights; that optimiser's step count goes up by one. */
+int  gm_ppo_learner_step_pi(gm_ppo_learner* l);
+int  gm_ppo_learner_step_vf(gm_ppo_learner* l);
+/* The held gradient in gm_ac_create's flat order and loss_pi, loss_v, kl, ent, cf (scalars[5]).
+ * Host pointers; either may be NULL. */
+int  gm_ppo_learner_read(gm_ppo_learner* l, float* grad_flat, float* scalars);
+/* Both optimisers' state in flat order, the policy's entries (actor, log_std) from pi_optimiser
+ * and the critic's from vf_optimiser: steps[2] = {pi, vf}.  Host pointers; any may be NULL. */
+int  gm_ppo_learner_get_state(gm_ppo_learner* l, int64_t* steps, float* exp_avg, float* exp_avg_sq,
+                              float* max_exp_avg_sq);
+int  gm_ppo_learner_set_state(gm_ppo_learner* l, const int64_t* steps, const float* exp_avg,
+                              const float* exp_avg_sq, const float* max_exp_avg_sq);
+/* The whole optimise_model on the first n_steps rows of traj, enqueued with one host read at the end:
+ *   gm_ac_gae(gamma, lam) -> gm_ac_adv_normalise
+ *   -> train_pi_iters x { gm_ppo_learner_grad_pi -> the KL stop -> gm_ppo_learner_step_pi }
+ *   -> train_vf_iters x { gm_ppo_learner_grad_vf -> gm_ppo_learner_step_vf }
+ * the same kernels in the same order as the calls, so every result equals theirs bit for bit.  The
+ * stop is the reference's: the first policy iteration whose kl > max_kl_ratio * target_kl takes no
+ * step and ends the policy loop; it latches on the device, the later launches are no-ops and the
+ * host reads the count of steps taken once, with info (may be NULL).  Advantages and returns live
+ * in the learner (grown to n_steps * n_envs floats each on demand). */
+int  gm_ppo_learner_update(gm_ppo_learner* l, const gm_ac_traj* traj, int n_steps, gm_ppo_info* info);
 
 #ifdef __cplusplus
 }
