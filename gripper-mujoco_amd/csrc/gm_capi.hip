@@ -25,6 +25,7 @@
 #include "gm_learn.hip"
 #include "gm_ac.hip"
 #include "gm_ppo_learn.hip"
+#include "gm_sac.hip"
 
 // calibration translation unit (gm_calib.hip)
 hipError_t gm_cal_launch_step(int n_seg, int n_envs, hipStream_t st, GmEnvState* states, const gm_model* m,
@@ -2348,6 +2349,377 @@ int gm_ppo_learner_update(gm_ppo_learner* l, const gm_ac_traj* traj, int n_steps
     std::memcpy(info->first, h.rows, sizeof(float) * GQ_SCALARS);
     std::memcpy(info->last, h.rows + GQ_SCALARS, sizeof(float) * GQ_SCALARS);
   }
+  return GM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- on-device SAC (collection side)
+struct gm_sac {
+  gm_ctx* ctx = nullptr;
+  GsNet net{};
+  int64_t total = 0;           // packed floats
+  int64_t n_raw = 0;           // floats of the caller's (parameters() order) parameters
+  std::vector<int32_t> pisz, qsz;
+  DevBuf<float> d_params;
+  // what gm_sac_act leaves (gm_sac_read): [n_envs][n_act] each, logp [n_envs]
+  DevBuf<float> d_act, d_logp, d_u, d_mu, d_ls;
+  DevBuf<GsArgs> d_args;       // gm_sac_rollout's launch arguments
+  DevBuf<GrArgs> d_rep;        // and its memory as replay_record's second half sees it
+  // gm_sac_target's a2 and logp2 where the caller keeps none (grown on demand)
+  DevBuf<float> d_ta2, d_tlogp;
+  int t_cap = 0;
+};
+
+// the layout of [pi | q1 | q2] for pi_sizes = [n_obs, *hidden, n_act] and q_sizes: the packed
+// float count, or -1; head: pi's sizes with the stacked output layer
+static int64_t sac_layout(const int32_t* pisz, int npi, const int32_t* qsz, int nq, GsNet* net, int64_t* n_raw,
+                          std::vector<int32_t>* head) {
+  if (!pisz || !qsz || npi < 2 || nq < 2) return -1;
+  const int na = pisz[npi - 1];
+  if (na < 1 || na > GA_MAX_ACT || qsz[0] != pisz[0] + na || qsz[nq - 1] != 1) return -1;
+  std::vector<int32_t> h(pisz, pisz + npi);
+  h[npi - 1] = 2 * na;
+  GsNet N{};
+  const int64_t tp = gl_layout(h.data(), npi, &N.pi);
+  const int64_t tq = gl_layout(qsz, nq, &N.q);
+  if (tp < 0 || tq < 0) return -1;
+  N.n_act = na;
+  N.q1_off = tp;
+  N.q2_off = tp + tq;
+  if (net) *net = N;
+  if (n_raw) *n_raw = gl_flat_count(N.pi) + 2 * gl_flat_count(N.q);
+  if (head) *head = h;
+  return tp + 2 * tq;
+}
+static bool sac_replay_ok(const gm_sac_replay* r) {
+  return r && r->capacity >= 1 && r->state && r->action && r->next_state && r->reward && r->end;
+}
+// the two device views of a caller's memory for a call of n_steps env-steps that starts after
+// row0 pushed transitions (G: state and action rows; R: replay_record's / the DQN push's view,
+// its action NULL); false with the message what for a memory the call cannot use
+static bool sac_replay_args(gm_ctx* c, const gm_sac_replay* r, int64_t row0, int n_steps, const char* what, GsReplay& G,
+                            GrArgs& R) {
+  if (!sac_replay_ok(r) || row0 < 0) {
+    fail(c, GM_E_ARG, std::string(what) + ": incomplete replay memory or negative row0");
+    return false;
+  }
+  if ((int64_t)n_steps * c->n_envs > r->capacity) {
+    fail(c, GM_E_ARG, std::string(what) + ": " + std::to_string(n_steps) + " env-steps of " + std::to_string(c->n_envs) +
+                          " envs would write a row of the replay memory twice (capacity " +
+                          std::to_string((long long)r->capacity) + ")");
+    return false;
+  }
+  const long long r0 = (long long)(row0 % r->capacity);
+  G = GsReplay{r->state, r->action, (long long)r->capacity, r0};
+  R = GrArgs{r->state, nullptr, r->next_state, r->reward, r->end, (long long)r->capacity, r0, c->cfg.n_obs, 0};
+  return true;
+}
+static hipError_t sac_launch_actor(gm_ctx* c, const gm_sac* p, const float* obs, int n, long long id0, int mode,
+                                   uint64_t seed, uint64_t decision, const GsActOut& out) {
+  hipLaunchKernelGGL(gm_sac_actor_kernel, dim3((n + GP_TILE - 1) / GP_TILE), dim3(64), 0, c->stream, obs, n, id0,
+                     p->d_params.get(), p->net, mode, seed, decision, out);
+  return hipGetLastError();
+}
+static bool sac_mode_ok(int mode) { return mode == GM_SAC_MEAN || mode == GM_SAC_SAMPLE || mode == GM_SAC_RANDOM; }
+
+extern "C" {
+
+void gm_sac_opt_default(gm_sac_opt* out) {
+  if (!out) return;
+  *out = gm_sac_opt{GP_ACT_RELU, 1.0f, -20.0f, 2.0f};
+}
+
+int64_t gm_sac_struct_size(int which) {
+  switch (which) {
+    case 0: return (int64_t)sizeof(gm_sac_replay);
+    case 1: return (int64_t)sizeof(gm_sac_batch);
+    case 2: return (int64_t)sizeof(gm_sac_opt);
+    default: return -1;
+  }
+}
+
+int64_t gm_sac_pack(const int32_t* pi_sizes, int n_pi, const int32_t* q_sizes, int n_q, int activation,
+                    const float* params, float* out, int64_t* offsets) {
+  GsNet N;
+  std::vector<int32_t> head;
+  if (activation != GP_ACT_RELU && activation != GP_ACT_TANH) return -1;
+  const int64_t total = sac_layout(pi_sizes, n_pi, q_sizes, n_q, &N, nullptr, &head);
+  if (total < 0) return total;
+  if (offsets) { offsets[0] = N.q1_off; offsets[1] = N.q2_off; }
+  if (!out) return total;
+  if (!params) return GM_E_ARG;
+  // the flat order already is the stacked layer's: mu_layer.W, mu_layer.b, log_std_layer.W,
+  // log_std_layer.b -> W = [mu W; log_std W] [2 n_act x in], b = [mu b; log_std b]
+  const int na = N.n_act, hin = pi_sizes[n_pi - 2];
+  int64_t hidden = 0;
+  for (int l = 0; l + 2 < n_pi; l++) hidden += (int64_t)pi_sizes[l + 1] * pi_sizes[l] + pi_sizes[l + 1];
+  std::vector<float> pi((size_t)gl_flat_count(N.pi));
+  std::memcpy(pi.data(), params, sizeof(float) * (size_t)hidden);
+  const float* mu_w = params + hidden;
+  const float* mu_b = mu_w + (size_t)na * hin;
+  const float* ls_w = mu_b + na;
+  const float* ls_b = ls_w + (size_t)na * hin;
+  float* w = pi.data() + hidden;
+  std::memcpy(w, mu_w, sizeof(float) * (size_t)na * hin);
+  std::memcpy(w + (size_t)na * hin, ls_w, sizeof(float) * (size_t)na * hin);
+  std::memcpy(w + (size_t)2 * na * hin, mu_b, sizeof(float) * (size_t)na);
+  std::memcpy(w + (size_t)2 * na * hin + na, ls_b, sizeof(float) * (size_t)na);
+  gm_policy_pack(head.data(), n_pi, pi.data(), out);
+  const float* q = params + gl_flat_count(N.pi);
+  gm_policy_pack(q_sizes, n_q, q, out + N.q1_off);
+  gm_policy_pack(q_sizes, n_q, q + gl_flat_count(N.q), out + N.q2_off);
+  return total;
+}
+
+int gm_sac_create(gm_ctx* c, const int32_t* pi_sizes, int n_pi, const int32_t* q_sizes, int n_q, const gm_sac_opt* opt,
+                  const float* params, gm_sac** out) {
+  if (!c || !pi_sizes || !q_sizes || !params || !out || n_pi < 2 || n_q < 2) return GM_E_ARG;
+  gm_sac_opt o;
+  gm_sac_opt_default(&o);
+  if (opt) o = *opt;
+  if (o.activation != GP_ACT_RELU && o.activation != GP_ACT_TANH)
+    return fail(c, GM_E_ARG, "gm_sac_create: activation must be 0 (ReLU) or 1 (Tanh)");
+  if (!(o.action_limit > 0.0f) || !(o.log_std_min <= o.log_std_max))
+    return fail(c, GM_E_ARG, "gm_sac_create: action_limit > 0 and log_std_min <= log_std_max expected");
+  GsNet N;
+  int64_t n_raw = 0;
+  const int64_t total = sac_layout(pi_sizes, n_pi, q_sizes, n_q, &N, &n_raw, nullptr);
+  if (total < 0)
+    return fail(c, GM_E_ARG, "gm_sac_create: <= 8 layers of width 1..256, n_actions <= " + std::to_string(GA_MAX_ACT) +
+                                 " and critics that map n_obs + n_actions to 1 expected");
+  if (!c->cfg.s.continous_actions)
+    return fail(c, GM_E_ARG, "gm_sac_create: the squashed Gaussian actor needs continuous actions (continous_actions != 0)");
+  if (N.pi.width[0] != c->cfg.n_obs || N.n_act != c->cfg.n_actions)
+    return fail(c, GM_E_ARG, "gm_sac_create: the actor must map n_obs (" + std::to_string(c->cfg.n_obs) +
+                                 ") to n_actions (" + std::to_string(c->cfg.n_actions) + ")");
+  N.act = o.activation;
+  N.limit = o.action_limit;
+  N.ls_min = o.log_std_min;
+  N.ls_max = o.log_std_max;
+  HIPCHK(c, hipSetDevice(c->device));
+  gm_sac* p = new gm_sac;
+  p->ctx = c;
+  p->net = N;
+  p->total = total;
+  p->n_raw = n_raw;
+  p->pisz.assign(pi_sizes, pi_sizes + n_pi);
+  p->qsz.assign(q_sizes, q_sizes + n_q);
+  const size_t rows = (size_t)c->n_envs * N.n_act;
+  hipError_t e = p->d_params.alloc((size_t)total);
+  if (e == hipSuccess) e = p->d_args.alloc(1);
+  if (e == hipSuccess) e = p->d_rep.alloc(1);
+  if (e == hipSuccess) e = p->d_act.alloc(rows);
+  if (e == hipSuccess) e = p->d_u.alloc(rows);
+  if (e == hipSuccess) e = p->d_mu.alloc(rows);
+  if (e == hipSuccess) e = p->d_ls.alloc(rows);
+  if (e == hipSuccess) e = p->d_logp.alloc((size_t)c->n_envs);
+  if (e != hipSuccess) {
+    gm_sac_destroy(p);
+    return fail(c, GM_E_HIP, std::string("gm_sac_create: ") + hipGetErrorString(e));
+  }
+  const int rc = gm_sac_set_params(p, params);
+  if (rc != GM_OK) { gm_sac_destroy(p); return rc; }
+  *out = p;
+  return GM_OK;
+}
+
+void gm_sac_destroy(gm_sac* p) {
+  if (!p) return;
+  if (p->ctx) {
+    (void)hipSetDevice(p->ctx->device);
+    (void)hipStreamSynchronize(p->ctx->stream);
+  }
+  delete p;
+}
+
+int gm_sac_set_params(gm_sac* p, const float* params) {
+  if (!p || !p->ctx || !params) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<float> packed((size_t)p->total);
+  gm_sac_pack(p->pisz.data(), (int)p->pisz.size(), p->qsz.data(), (int)p->qsz.size(), p->net.act, params,
+              packed.data(), nullptr);
+  return stage_upload(c, p->d_params, packed.data(), sizeof(float) * (size_t)p->total);
+}
+
+int gm_sac_get_packed(gm_sac* p, float* packed) {
+  if (!p || !p->ctx || !packed) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  return read_back(c, packed, p->d_params, sizeof(float) * (size_t)p->total);
+}
+
+int gm_sac_get_params(gm_sac* p, float* flat) {
+  if (!p || !p->ctx || !flat) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  std::vector<float> packed((size_t)p->total);
+  const int rc = gm_sac_get_packed(p, packed.data());
+  if (rc != GM_OK) return rc;
+  // the inverse of gm_sac_pack: the stacked head back into mu_layer and log_std_layer
+  const GsNet& N = p->net;
+  const int na = N.n_act, L = N.pi.n_layers, hin = N.pi.width[L - 1];
+  int64_t hidden = 0;
+  for (int l = 0; l + 1 < L; l++) hidden += (int64_t)N.pi.width[l + 1] * N.pi.width[l] + N.pi.width[l + 1];
+  std::vector<float> pi((size_t)gl_flat_count(N.pi));
+  gl_for_each_param(N.pi, [&](int64_t i, int64_t k) { pi[(size_t)i] = packed[(size_t)k]; });
+  std::memcpy(flat, pi.data(), sizeof(float) * (size_t)hidden);
+  const float* w = pi.data() + hidden;
+  float* dst = flat + hidden;
+  std::memcpy(dst, w, sizeof(float) * (size_t)na * hin);                                        // mu_layer.W
+  std::memcpy(dst + (size_t)na * hin, w + (size_t)2 * na * hin, sizeof(float) * (size_t)na);    // mu_layer.b
+  std::memcpy(dst + (size_t)na * hin + na, w + (size_t)na * hin, sizeof(float) * (size_t)na * hin);       // log_std_layer.W
+  std::memcpy(dst + (size_t)2 * na * hin + na, w + (size_t)2 * na * hin + na, sizeof(float) * (size_t)na);   // .b
+  float* q = flat + gl_flat_count(N.pi);
+  const int64_t nq = gl_flat_count(N.q);
+  gl_for_each_param(N.q, [&](int64_t i, int64_t k) {
+    q[(size_t)i] = packed[(size_t)(N.q1_off + k)];
+    q[(size_t)(nq + i)] = packed[(size_t)(N.q2_off + k)];
+  });
+  return GM_OK;
+}
+
+int gm_sac_act(gm_sac* p, int mode, uint64_t seed, uint64_t decision) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  if (!sac_mode_ok(mode)) return fail(c, GM_E_ARG, "gm_sac_act: mode must be GM_SAC_MEAN, GM_SAC_SAMPLE or GM_SAC_RANDOM");
+  HIPCHK(c, hipSetDevice(c->device));
+  const GsActOut out{p->d_act, p->d_logp, p->d_u, p->d_mu, p->d_ls};
+  HIPCHK(c, sac_launch_actor(c, p, c->d_obs, c->n_envs, c->env_offset, mode, seed, decision, out));
+  return gm_set_action(c, p->d_act, 1);
+}
+
+int gm_sac_read(gm_sac* p, float* act, float* logp, float* u, float* mu, float* log_std) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t rows = sizeof(float) * (size_t)c->n_envs * p->net.n_act;
+  const struct { float* dst; const float* src; size_t bytes; } cp[] = {
+      {act, p->d_act, rows}, {logp, p->d_logp, sizeof(float) * (size_t)c->n_envs}, {u, p->d_u, rows},
+      {mu, p->d_mu, rows}, {log_std, p->d_ls, rows}};
+  for (const auto& x : cp)
+    if (x.dst) HIPCHK(c, hipMemcpyAsync(x.dst, x.src, x.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GM_OK;
+}
+
+int gm_sac_push_begin(gm_sac* p, const gm_sac_replay* replay, int64_t row0) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  GsReplay G;
+  GrArgs R;
+  if (!sac_replay_args(c, replay, row0, 1, "gm_sac_push_begin", G, R)) return GM_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, launch_per_obs_element(c, (long long)c->n_envs * c->cfg.n_obs, gm_sac_push_begin_kernel, c->d_obs,
+                                   p->d_act.get(), c->n_envs, c->cfg.n_obs, p->net.n_act, G));
+  return GM_OK;
+}
+
+int gm_sac_push_end(gm_sac* p, const gm_sac_replay* replay, int64_t row0, int max_episode_steps) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  GsReplay G;
+  GrArgs R;
+  if (!sac_replay_args(c, replay, row0, 1, "gm_sac_push_end", G, R)) return GM_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  // (the DQN memory's second half: it writes next_state, reward and end, no action)
+  HIPCHK(c, launch_per_obs_element(c, (long long)c->n_envs * c->cfg.n_obs, gm_replay_push_end_kernel, c->d_obs,
+                                   c->d_state.get(), c->d_rew, c->d_done, c->n_envs, max_episode_steps, R));
+  return GM_OK;
+}
+
+int gm_sac_rollout(gm_sac* p, int n_steps, int mode, uint64_t seed, uint64_t decision0, int max_episode_steps,
+                   gm_episode_end* records, const gm_sac_replay* replay, int64_t row0) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  if (n_steps < 1 || !sac_mode_ok(mode))
+    return fail(c, GM_E_ARG, "gm_sac_rollout: n_steps >= 1 and mode GM_SAC_MEAN, GM_SAC_SAMPLE or GM_SAC_RANDOM expected");
+  GsReplay G{};
+  GrArgs R{};
+  if (replay && !sac_replay_args(c, replay, row0, n_steps, "gm_sac_rollout", G, R)) return GM_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (chunk_queue_on(c)) {
+    GsArgs A{};
+    A.net = p->net;
+    A.params = p->d_params;
+    A.rep = G;
+    A.mode = mode;
+    A.seed = seed;
+    A.decision0 = decision0;
+    int rc = stage_upload(c, p->d_args, &A, sizeof(GsArgs));
+    if (rc == GM_OK && replay) rc = stage_upload(c, p->d_rep, &R, sizeof(GrArgs));
+    if (rc != GM_OK) return rc;
+    GmRolloutJob job = rollout_job(c, n_steps, GM_DRV_SAC, seed, 0.0f, max_episode_steps, records);
+    job.sac = p->d_args;
+    job.replay = replay ? p->d_rep.get() : nullptr;
+    return timed_launch(c, &job);
+  }
+  return per_step_rollout(
+      c, n_steps, max_episode_steps, records,
+      [&](int k) {
+        const int rc = gm_sac_act(p, mode, seed, decision0 + (uint64_t)k);
+        return rc == GM_OK && replay ? gm_sac_push_begin(p, replay, row0 + (int64_t)k * c->n_envs) : rc;
+      },
+      [&](int k) {
+        return replay ? gm_sac_push_end(p, replay, row0 + (int64_t)k * c->n_envs, max_episode_steps) : (int)GM_OK;
+      });
+}
+
+int gm_sac_replay_sample(gm_ctx* c, const gm_sac_replay* replay, int64_t size, int batch, uint64_t seed, uint64_t draw,
+                         const gm_sac_batch* out) {
+  if (!c) return GM_E_ARG;
+  if (!sac_replay_ok(replay) || !out || !out->state || !out->action || !out->next_state || !out->reward || !out->end ||
+      !out->index)
+    return fail(c, GM_E_ARG, "gm_sac_replay_sample: incomplete replay memory or batch arrays");
+  if (size < 1 || size > replay->capacity || size > 0x7FFFFFFFll || batch < 1 || batch > size)
+    return fail(c, GM_E_ARG, "gm_sac_replay_sample: batch " + std::to_string(batch) + " of " +
+                                 std::to_string((long long)size) + " stored transitions (capacity " +
+                                 std::to_string((long long)replay->capacity) + "): 1 <= batch <= size <= capacity expected");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, launch_per_obs_element(c, (long long)batch * c->cfg.n_obs, gm_sac_replay_sample_kernel, *replay,
+                                   c->cfg.n_obs, c->cfg.n_actions, (long long)size, batch, gr_key(seed, draw), *out));
+  return GM_OK;
+}
+
+int gm_sac_q(gm_sac* p, const float* state, const float* action, int n, float* q1, float* q2) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  if (!state || !action || n < 1) return fail(c, GM_E_ARG, "gm_sac_q: no state or action array, or n < 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(gm_sac_q_kernel, dim3((n + GP_TILE - 1) / GP_TILE), dim3(64), 0, c->stream, state, action, n,
+                     p->d_params.get(), p->net, q1, q2, GsBackup{});
+  HIPCHK(c, hipGetLastError());
+  return GM_OK;
+}
+
+int gm_sac_target(gm_sac* target, gm_sac* online, const gm_sac_batch* batch, int n, float gamma, float alpha,
+                  int bootstrap_truncated, uint64_t seed, uint64_t draw, float* y, float* a2, float* u2, float* logp2,
+                  float* qmin) {
+  if (!target || !target->ctx || !online) return GM_E_ARG;
+  gm_ctx* c = target->ctx;
+  if (online->ctx != c) return fail(c, GM_E_ARG, "gm_sac_target: the two handles belong to different contexts");
+  if (online->pisz != target->pisz || online->qsz != target->qsz)
+    return fail(c, GM_E_ARG, "gm_sac_target: the two handles have different network sizes");
+  if (!batch || !batch->next_state || !batch->reward || !batch->end || !y || n < 1)
+    return fail(c, GM_E_ARG, "gm_sac_target: incomplete batch (next_state, reward, end), no y or n < 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int na = target->net.n_act;
+  if ((!a2 || !logp2) && n > target->t_cap) {
+    // (the stream may still read the old arrays: wait before freeing them)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    target->t_cap = 0;
+    HIPCHK(c, target->d_ta2.alloc((size_t)n * na));
+    HIPCHK(c, target->d_tlogp.alloc((size_t)n));
+    target->t_cap = n;
+  }
+  float* a = a2 ? a2 : target->d_ta2.get();
+  float* lp = logp2 ? logp2 : target->d_tlogp.get();
+  HIPCHK(c, sac_launch_actor(c, online, batch->next_state, n, 0, GM_SAC_SAMPLE, seed, draw,
+                             GsActOut{a, lp, u2, nullptr, nullptr}));
+  const GsBackup B{batch->reward, batch->end, lp, gamma, alpha, bootstrap_truncated, 0, y, qmin};
+  hipLaunchKernelGGL(gm_sac_q_kernel, dim3((n + GP_TILE - 1) / GP_TILE), dim3(64), 0, c->stream, batch->next_state,
+                     (const float*)a, n, target->d_params.get(), target->net, (float*)nullptr, (float*)nullptr, B);
+  HIPCHK(c, hipGetLastError());
   return GM_OK;
 }
 

@@ -8,6 +8,7 @@
 #include "gm_policy_net.h"
 #include "gm_ac_net.h"
 #include "gm_replay.h"
+#include "gm_sac_net.h"
 
 #define GM_CQ_NB 16      // priority buckets per XCD
 // The job every env of a launch runs: `steps` env-steps in a row, each the per-step API's sequence:
@@ -19,7 +20,8 @@ enum GmDriver {              // gm_rollout_params::action_mode for the scripted 
   GM_DRV_DQN = 2,            // the DQN policy picks a discrete action (gm_policy_rollout)
   GM_DRV_PROGRAM = 3,        // grasp program (gm_program_actions)
   GM_DRV_MIX = 4,            // the program in 1 episode of 4, the scripted mix otherwise
-  GM_DRV_AC = 5              // the PPO actor-critic samples continuous actions (gm_ac_rollout)
+  GM_DRV_AC = 5,             // the PPO actor-critic samples continuous actions (gm_ac_rollout)
+  GM_DRV_SAC = 6             // the SAC squashed actor samples continuous actions (gm_sac_rollout)
 };
 struct GmRolloutJob {
   int steps, driver;         // driver: GmDriver
@@ -36,8 +38,12 @@ struct GmRolloutJob {
   GpNet pnet;
   const float* peps;         // [steps] exploration threshold per env-step of the launch,
   uint64_t pdecision;        // the first env-step's decision index
-  const GaArgs* ac;          // GM_DRV_AC: device copy of the launch's arguments
-  const GrArgs* replay;      // GM_DRV_DQN: device copy of the replay memory to record into (NULL: none)
+  union {                    // device copy of the launch's arguments: one slot, so that both reach
+    const GaArgs* ac;        // GM_DRV_AC's ...
+    const GsArgs* sac;       // ... and GM_DRV_SAC's driver through the one call of ac_rollout_driver
+  };
+  const GrArgs* replay;      // GM_DRV_DQN: device copy of the replay memory to record into (NULL: none);
+                             // GM_DRV_SAC: the same with a NULL action, for the second half of its push
 };
 struct GmChunkCarry {        // what a chunk hands the next besides the hot state
   int32_t sub_done, nsub;

@@ -2,7 +2,9 @@
 // gp_forward_tile for 16 envs per wave and gp_forward_one for one env on its own wave) and the
 // DQN action selection on top of it ("fused on-device DQN inference").
 // The DQN callers (gm_policy_kernel, gp_select_one) pass GP_ACT_RELU as a constant; the PPO
-// actor-critic (gm_ac_net.h, gm_ac.hip, ac_rollout_driver) passes each net's run-time code.
+// actor-critic (gm_ac_net.h, gm_ac.hip, ac_rollout_driver) and SAC (gm_sac_net.h, gm_sac.hip,
+// sac_rollout_driver) pass each net's run-time code.  gp_forward_tile is its load of the rows
+// followed by gp_layers_tile, which the SAC critics call on rows they assemble themselves.
 //
 // Reference: rl/networks.py:7-41 VariableNetwork.forward (Linear + ReLU per hidden
 // layer, a final Linear, Softmax over dim 1) and rl/agents/DQN.py:184-209
@@ -88,24 +90,12 @@ __device__ __forceinline__ int gp_choose(const float* x, int n_out, float eps, u
   return best;
 }
 
-// One net's forward for a tile of 16 envs, one wave per tile (gm_policy_kernel, gm_ac_kernel):
-// observations of envs e0 .. e0 + 15 of obs[n_envs][n_obs] -> act[cur][env row][output]; returns
-// cur.  Hidden layers get gp_activate(code), the last layer none.  copy, when non-NULL, receives
-// the observations as loaded ([n_envs][n_obs]).  The leading barrier lets a second net reuse
-// the rows once every lane has read the first one's outputs.
-__device__ __forceinline__ int gp_forward_tile(const float* __restrict__ obs, float* __restrict__ copy, int e0,
-                                               int n_envs, const float* __restrict__ params, const GpNet& P, int code,
-                                               float (*act)[GP_TILE][GP_ROW], int lane) {
-  const int n_obs = P.width[0];
-  const int k0 = P.kpad[0];
-  __syncthreads();
-  for (int i = lane; i < GP_TILE * k0; i += 64) {
-    const int r = i / k0, k = i - r * k0;
-    const bool in = e0 + r < n_envs && k < n_obs;
-    const float o = in ? obs[(size_t)(e0 + r) * n_obs + k] : 0.0f;
-    act[0][r][k] = o;
-    if (copy && in) copy[(size_t)(e0 + r) * n_obs + k] = o;
-  }
+// The layers of gp_forward_tile on rows already in act[0] ([16][kpad[0]], zero where a row or a
+// column is padding; written by any lanes of the workgroup: the leading barrier orders them):
+// the only MFMA loop of the tile form.  gm_sac.hip's critic kernel assembles [state | action]
+// rows there itself.  Returns cur.
+__device__ __forceinline__ int gp_layers_tile(const float* __restrict__ params, const GpNet& P, int code,
+                                              float (*act)[GP_TILE][GP_ROW], int lane) {
   __syncthreads();
   int cur = 0;
   for (int l = 0; l < P.n_layers; l++) {
@@ -136,6 +126,27 @@ __device__ __forceinline__ int gp_forward_tile(const float* __restrict__ obs, fl
     cur ^= 1;
   }
   return cur;
+}
+
+// One net's forward for a tile of 16 envs, one wave per tile (gm_policy_kernel, gm_ac_kernel):
+// observations of envs e0 .. e0 + 15 of obs[n_envs][n_obs] -> act[cur][env row][output]; returns
+// cur.  Hidden layers get gp_activate(code), the last layer none.  copy, when non-NULL, receives
+// the observations as loaded ([n_envs][n_obs]).  The leading barrier lets a second net reuse
+// the rows once every lane has read the first one's outputs.
+__device__ __forceinline__ int gp_forward_tile(const float* __restrict__ obs, float* __restrict__ copy, int e0,
+                                               int n_envs, const float* __restrict__ params, const GpNet& P, int code,
+                                               float (*act)[GP_TILE][GP_ROW], int lane) {
+  const int n_obs = P.width[0];
+  const int k0 = P.kpad[0];
+  __syncthreads();
+  for (int i = lane; i < GP_TILE * k0; i += 64) {
+    const int r = i / k0, k = i - r * k0;
+    const bool in = e0 + r < n_envs && k < n_obs;
+    const float o = in ? obs[(size_t)(e0 + r) * n_obs + k] : 0.0f;
+    act[0][r][k] = o;
+    if (copy && in) copy[(size_t)(e0 + r) * n_obs + k] = o;
+  }
+  return gp_layers_tile(params, P, code, act, lane);
 }
 
 // The same forward for ONE env on its own wave (gm_rollout's drivers, gm_rollout.h

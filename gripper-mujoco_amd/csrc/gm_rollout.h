@@ -1,6 +1,6 @@
 // gm_rollout.h -- the chunked env-step's rollout job: the scripted / random / program drivers
 // (gm_scripted_actions, gm_random_actions, gm_program_actions), the actor-critic driver, the
-// in-kernel auto-reset and chunked_env_steps, a resident wave's loop over the queue's jobs.
+// SAC driver, the in-kernel auto-reset and chunked_env_steps, a resident wave's loop over the queue's jobs.
 // SharedT: s through the stages it calls; st (activations, spawn buffers), stp_fixed, work_*.
 #pragma once
 #include "gm_substep.h"
@@ -10,6 +10,7 @@
 #include "gm_policy_net.h"
 #include "gm_ac_net.h"
 #include "gm_replay.h"
+#include "gm_sac_net.h"
 
 // ------------------------------ chunked env-step: the rollout job (its work queue: gm_chunkq.h)
 // the grasp program's inputs (gm_state.h gm_program_fraction) from an env's state and its
@@ -65,6 +66,43 @@ __device__ __noinline__ void driver_actions(GmEnvHot& s, RingRef R, const gm_mod
   for (int i = 0; i < na; i++) set_action_one(s, m, C, i, f[i]);
 }
 
+// GM_DRV_SAC (gm_sac_rollout): the SAC actor's part of one env's env-step on the env's own wave,
+// called at the begin of an env-step only (through ac_rollout_driver's phase 3): gm_sac_act on this env alone and gm_sac_push_begin's
+// row -- the observation into the memory's state row (as loaded for the forward), the head row
+// through gs_sample, the squashed action into the action row, then lane 0 applies the clipped
+// actions in order.  gm_sac_push_end's half is replay_record's phase 1 through J.replay (it needs
+// no action), so the end of an env-step has no SAC code.  scratch: 2 x GP_ROW floats of LDS; the
+// row the forward did not leave its outputs in holds a and u (2 n_act <= GP_ROW floats).
+__device__ __noinline__ void sac_rollout_driver(const GsArgs* __restrict__ Ap, const float* obs, int env, int n_envs,
+                                                int k, int64_t gid, float* scratch, GmEnvHot& s,
+                                                const gm_model* __restrict__ m, const gm_config* __restrict__ C,
+                                                int lane) {
+  const GsArgs& A = *Ap;
+  static_assert(2 * GA_MAX_ACT <= GP_ROW, "a and u fit one activation row");
+  const int n_obs = A.net.pi.width[0];
+  const int na = A.net.n_act;
+  const size_t row = A.rep.state ? (size_t)gr_row(A.rep.row0, k, n_envs, env, A.rep.capacity) : 0;
+  float* srow = A.rep.state ? A.rep.state + row * (size_t)n_obs : nullptr;
+  int cur = 0;
+  if (A.mode != GM_SAC_RANDOM) {
+    cur = gp_forward_one(obs, srow, A.params, A.net.pi, A.net.act, scratch, lane);
+  } else if (srow) {   // (replay_record's read: the wave's stores drained, then agent-scope loads)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    for (int j = lane; j < n_obs; j += 64) srow[j] = __hip_atomic_load(obs + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (lane == 0) {
+    float* a = scratch + (cur ^ 1) * GP_ROW;
+    gs_sample(scratch + cur * GP_ROW, na, A.mode, A.net.limit, A.net.ls_min, A.net.ls_max, A.seed,
+              A.decision0 + (uint64_t)k, (uint64_t)gid, a, a + GA_MAX_ACT, nullptr);
+    for (int i = 0; i < na; i++) {
+      float f = a[i];
+      if (A.rep.action) A.rep.action[row * (size_t)na + i] = f;
+      if (f < -1.0f) f = -1.0f; else if (f > 1.0f) f = 1.0f;
+      set_action_one(s, m, C, i, f);
+    }
+  }
+}
+
 // GM_DRV_AC (gm_ac_rollout): the actor-critic's part of one env's env-step on the env's own
 // wave, kept out of the substep loop's instruction stream (called between env-steps only).
 //   phase 0, before the env-step: gm_ac_act on this env alone -- observation, mu, the sampled
@@ -74,11 +112,17 @@ __device__ __noinline__ void driver_actions(GmEnvHot& s, RingRef R, const gm_mod
 //     and, for a truncated env only, the critic on the post-step observation;
 //   phase 2, after the env's last env-step: gm_ac_finish -- the critic on the observation left
 //     in the buffer (the reset one if the env was reset).
+//   phase 3: GM_DRV_SAC's begin of an env-step, handed on to sac_rollout_driver (Ap is the
+//     job's GsArgs then: GmRolloutJob's union), so that the kernel has one call site for both.
 // scratch: GA_ONE_FLOATS floats of LDS (the dynamics union, dead between env-steps).
 __device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restrict__ Ap, const float* obs, int env,
                                                int n_envs, int k, int max_ep, int64_t gid, float* scratch,
                                                GmEnvHot& s, const gm_model* __restrict__ m,
                                                const gm_config* __restrict__ C, int lane) {
+  if (phase == 3) {
+    sac_rollout_driver(reinterpret_cast<const GsArgs*>(Ap), obs, env, n_envs, k, gid, scratch, s, m, C, lane);
+    return;
+  }
   const GaArgs& A = *Ap;
   const size_t row = (size_t)k * (size_t)n_envs + (size_t)env;
   if (phase == 0) {
@@ -233,10 +277,12 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
             set_action_one(S.s, m, C, a, 0.0f);
             S.stp_fixed = 0;
           }
-        } else if (J.driver == GM_DRV_AC) {
+        } else if (J.driver == GM_DRV_AC || J.driver == GM_DRV_SAC) {
           static_assert(sizeof(S.st) >= sizeof(float) * GA_ONE_FLOATS, "actor-critic activations fit the union");
-          ac_rollout_driver(0, J.ac, o, env, n_envs, cr.step_idx, J.max_ep, rollout_gid(J, env),
-                            reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
+          // (one call for both: a call site of its own for sac_rollout_driver cost the DUO
+          // instantiations N + 2 = 7 / 8 / 9 a VGPR and N + 2 = 12 DUO 16 B of scratch)
+          ac_rollout_driver(J.driver == GM_DRV_SAC ? 3 : 0, J.ac, o, env, n_envs, cr.step_idx, J.max_ep,
+                            rollout_gid(J, env), reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
           if (lane == 0) S.stp_fixed = 0;
         } else if (lane == 0) {
           driver_actions(S.s, g->ring, m, C, J.driver, J.seed, J.jitter, rollout_gid(J, env));

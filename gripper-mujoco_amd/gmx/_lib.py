@@ -180,6 +180,27 @@ class PpoInfo(C.Structure):
     _fields_ = [("pi_iters_done", C.c_int32), ("pad", C.c_int32), ("first", C.c_float * 5), ("last", C.c_float * 5)]
 
 
+class SacOpt(C.Structure):
+    """gm_sac_opt (include/gripper_mi355x.h)."""
+    _fields_ = [("activation", C.c_int32), ("action_limit", C.c_float), ("log_std_min", C.c_float),
+                ("log_std_max", C.c_float)]
+
+
+class SacReplay(C.Structure):
+    """gm_sac_replay (include/gripper_mi355x.h): the transition memory with a float action row."""
+    _fields_ = [("capacity", C.c_int64), ("state", C.c_void_p), ("action", C.c_void_p), ("next_state", C.c_void_p),
+                ("reward", C.c_void_p), ("end", C.c_void_p)]
+
+
+class SacBatch(C.Structure):
+    """gm_sac_batch (include/gripper_mi355x.h)."""
+    _fields_ = [("state", C.c_void_p), ("action", C.c_void_p), ("next_state", C.c_void_p), ("reward", C.c_void_p),
+                ("end", C.c_void_p), ("index", C.c_void_p)]
+
+
+SAC_MEAN, SAC_SAMPLE, SAC_RANDOM = 0, 1, 2
+ACT_RELU, ACT_TANH = 0, 1
+
 OPT_ADAM, OPT_ADAMW = 0, 1
 LOSS_SMOOTH_L1, LOSS_MSE = 0, 1
 
@@ -240,6 +261,10 @@ def load_library(path: str | None = None):
             continue   # an older developer build without this struct
         if n != C.sizeof(cls):
             raise ImportError(f"struct layout mismatch for {cls.__name__}: C {n} vs ctypes {C.sizeof(cls)}")
+    for which, cls in {0: SacReplay, 1: SacBatch, 2: SacOpt}.items():
+        if getattr(lib, "gm_sac_struct_size", None) is not None and lib.gm_sac_struct_size(which) != C.sizeof(cls):
+            raise ImportError(f"struct layout mismatch for {cls.__name__}: C {lib.gm_sac_struct_size(which)} "
+                              f"vs ctypes {C.sizeof(cls)}")
     if path is None:
         _lib = lib
     return lib
@@ -363,6 +388,22 @@ def _declare(lib):
         "gm_ppo_learner_get_state": (i32, [vp, C.POINTER(C.c_int64), f32p, f32p, f32p]),
         "gm_ppo_learner_set_state": (i32, [vp, C.POINTER(C.c_int64), f32p, f32p, f32p]),
         "gm_ppo_learner_update": (i32, [vp, vp, i32, vp]),
+        "gm_sac_opt_default": (None, [vp]),
+        "gm_sac_struct_size": (C.c_int64, [i32]),
+        "gm_sac_pack": (C.c_int64, [i32p, i32, i32p, i32, i32, f32p, f32p, C.POINTER(C.c_int64)]),
+        "gm_sac_create": (i32, [vp, i32p, i32, i32p, i32, vp, f32p, C.POINTER(vp)]),
+        "gm_sac_destroy": (None, [vp]),
+        "gm_sac_set_params": (i32, [vp, f32p]),
+        "gm_sac_get_params": (i32, [vp, f32p]),
+        "gm_sac_get_packed": (i32, [vp, f32p]),
+        "gm_sac_act": (i32, [vp, i32, C.c_uint64, C.c_uint64]),
+        "gm_sac_read": (i32, [vp, f32p, f32p, f32p, f32p, f32p]),
+        "gm_sac_push_begin": (i32, [vp, vp, C.c_int64]),
+        "gm_sac_push_end": (i32, [vp, vp, C.c_int64, i32]),
+        "gm_sac_rollout": (i32, [vp, i32, i32, C.c_uint64, C.c_uint64, i32, vp, vp, C.c_int64]),
+        "gm_sac_replay_sample": (i32, [vp, vp, C.c_int64, i32, C.c_uint64, C.c_uint64, vp]),
+        "gm_sac_q": (i32, [vp, vp, vp, i32, vp, vp]),
+        "gm_sac_target": (i32, [vp, vp, vp, i32, C.c_float, C.c_float, i32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -1000,6 +1000,114 @@ int  gm_ppo_learner_set_state(gm_ppo_learner* l, const int64_t* steps, const flo
  * in the learner (grown to n_steps * n_envs floats each on demand). */
 int  gm_ppo_learner_update(gm_ppo_learner* l, const gm_ac_traj* traj, int n_steps, gm_ppo_info* info);
 
+/* ---- SAC: squashed Gaussian actor, action replay memory, twin critics and the soft Q target ----
+ * The collection side of Agent_SAC (rl/agents/ActorCritic.py) and everything of its
+ * optimise_model that is forward-only.  The learner (the backward of loss_q and loss_pi, the two
+ * optimisers, the polyak update) is not here.
+ *   actor    h = mlp([n_obs, *hidden], act, act)(obs): the activation follows every hidden Linear;
+ *            mu = mu_layer(h), log_std = clamp(log_std_layer(h), log_std_min, log_std_max);
+ *            u = mu + exp(log_std) z (GM_SAC_SAMPLE) or u = mu (GM_SAC_MEAN);
+ *            logp = sum_i Normal(mu, std).log_prob(u)_i - sum_i 2 (log 2 - u_i - softplus(-2 u_i));
+ *            a = action_limit tanh(u)
+ *   critics  q_j = mlp([n_obs + n_actions, *hidden, 1], act)(cat(obs, a)), j = 1, 2
+ * f32 on the DQN policy's MFMA forward.  The draws are the PPO sampler's counters, keyed by (seed,
+ * global env id, decision, action index): c_1, c_2 -> Box-Muller z; c_3 -> the uniform action
+ * 2 u3 - 1 of GM_SAC_RANDOM (select_action before random_start_episodes: the net is not used and
+ * u, logp, mu, log_std are written as 0).
+ * Flat parameter order (torch's parameters() order for MLPActorCriticAC): the actor's hidden
+ * layers W0 [out x in], b0, ..., mu_layer.W, b, log_std_layer.W, b, then q1's layers, then q2's. */
+#define GM_SAC_MEAN   0
+#define GM_SAC_SAMPLE 1
+#define GM_SAC_RANDOM 2
+typedef struct gm_sac_opt {
+  int32_t activation;     /* hidden activation of all three nets: 0 ReLU (default), 1 Tanh */
+  float   action_limit;   /* 1 */
+  float   log_std_min;    /* -20 */
+  float   log_std_max;    /* 2 */
+} gm_sac_opt;
+void gm_sac_opt_default(gm_sac_opt* out);
+/* The transition memory with a float action row; gm_replay's ring rules (row0, the row of env e at
+ * env-step k, no row written twice in a call) hold unchanged. */
+typedef struct gm_sac_replay {
+  int64_t  capacity;    /* rows */
+  float*   state;       /* [capacity][n_obs]      observation the action was chosen from */
+  float*   action;      /* [capacity][n_actions]  the squashed action the env received (before its clip) */
+  float*   next_state;  /* [capacity][n_obs]      observation after the env-step, never the reset one */
+  float*   reward;      /* [capacity] */
+  uint8_t* end;         /* [capacity]  0 episode continues, 1 terminal (done), 2 truncated only */
+} gm_sac_replay;
+typedef struct gm_sac_batch {
+  float*   state;       /* [batch][n_obs] */
+  float*   action;      /* [batch][n_actions] */
+  float*   next_state;  /* [batch][n_obs] */
+  float*   reward;      /* [batch] */
+  uint8_t* end;         /* [batch] */
+  int32_t* index;       /* [batch] the ring rows gathered */
+} gm_sac_batch;
+/* sizeof of 0 gm_sac_replay, 1 gm_sac_batch, 2 gm_sac_opt (-1 otherwise): for bindings */
+int64_t gm_sac_struct_size(int which);
+typedef struct gm_sac gm_sac;
+/* The device layout of the parameters: [pi | q1 | q2], each net in gm_policy_pack's layout; pi is
+ * the one MLP [n_obs, *hidden, 2 n_actions] whose output layer is mu_layer stacked over
+ * log_std_layer.  pi_sizes = [n_obs, *hidden, n_actions], q_sizes = [n_obs + n_actions, *hidden, 1].
+ * Returns the packed float count (out may be NULL: the count and the offsets only); offsets (may
+ * be NULL) receives the float offsets of q1 and q2.  Negative for unsupported sizes: a width above
+ * 256, more than 8 layers, n_actions above 40, q_sizes[0] != pi_sizes[0] + n_actions, a critic
+ * output other than 1 or an unknown activation.  Host only, no GPU needed. */
+int64_t gm_sac_pack(const int32_t* pi_sizes, int n_pi, const int32_t* q_sizes, int n_q, int activation,
+                    const float* params, float* out, int64_t* offsets);
+/* opt may be NULL (the defaults).  The env must have continuous actions and the actor must map
+ * n_obs to n_actions.  A target network (mlp_ac_targ) is a second handle created from the same
+ * parameters. */
+int  gm_sac_create(gm_ctx* ctx, const int32_t* pi_sizes, int n_pi, const int32_t* q_sizes, int n_q,
+                   const gm_sac_opt* opt, const float* params, gm_sac** out);
+void gm_sac_destroy(gm_sac* p);
+int  gm_sac_set_params(gm_sac* p, const float* params);
+int  gm_sac_get_params(gm_sac* p, float* flat);
+int  gm_sac_get_packed(gm_sac* p, float* packed);
+/* select_action for every env from its current observation (mode: GM_SAC_*), the draws at
+ * `decision`.  Keeps act, logp, u, mu and the clamped log_std in the handle's device arrays and
+ * applies the actions as gm_ac_act does: clipped to [-1, 1], set in order. */
+int  gm_sac_act(gm_sac* p, int mode, uint64_t seed, uint64_t decision);
+/* What the last gm_sac_act left: act, u, mu, log_std [n_envs][n_actions], logp [n_envs].  Host
+ * pointers; any may be NULL. */
+int  gm_sac_read(gm_sac* p, float* act, float* logp, float* u, float* mu, float* log_std);
+/* ReplayMemory.push in two halves around gm_step, by gm_policy_push_begin / _end's rules: the same
+ * ring row, the same end code, next_state the post-step observation before any reset. */
+int  gm_sac_push_begin(gm_sac* p, const gm_sac_replay* replay, int64_t row0);
+int  gm_sac_push_end(gm_sac* p, const gm_sac_replay* replay, int64_t row0, int max_episode_steps);
+/* The fused rollout.  For k = 0 .. n_steps - 1
+ *   gm_sac_act(mode, seed, decision0 + k) -> gm_sac_push_begin(row0 + k * n_envs) -> gm_step
+ *   -> gm_sac_push_end(row0 + k * n_envs, max_episode_steps)
+ *   -> gm_autoreset_episodes(max_episode_steps, spawn = NULL, records + k * n_envs)
+ * as ONE persistent launch of gm_rollout's kind: each env's own wave runs the actor between its
+ * env-steps.  State, observations, records and every array of the memory equal the per-step
+ * sequence's bit for bit; under GM_CHUNK_SUBSTEPS=0 it runs that sequence.  replay may be NULL
+ * (nothing is recorded; row0 is ignored).  records: device [n_steps][n_envs], may be NULL.  The
+ * caller advances its count of pushed transitions by n_steps * n_envs. */
+int  gm_sac_rollout(gm_sac* p, int n_steps, int mode, uint64_t seed, uint64_t decision0, int max_episode_steps,
+                    gm_episode_end* records, const gm_sac_replay* replay, int64_t row0);
+/* ReplayMemory.batch: gm_replay_indices' rows (the same keyed bijection) gathered into out's
+ * arrays, float action rows included, in one kernel. */
+int  gm_sac_replay_sample(gm_ctx* ctx, const gm_sac_replay* replay, int64_t size, int batch, uint64_t seed,
+                          uint64_t draw, const gm_sac_batch* out);
+/* Both critics on cat(state, action) for n rows: state [n][n_obs], action [n][n_actions] (two
+ * independent device arrays), q1, q2: device [n], either may be NULL. */
+int  gm_sac_q(gm_sac* p, const float* state, const float* action, int n, float* q1, float* q2);
+/* compute_loss_q's backup for the first n rows of a batch, no gradient involved:
+ *   a2, logp2 = online's actor on next_state, GM_SAC_SAMPLE, the draws keyed (seed, batch row i as
+ *               the id, `draw` as the decision) -- pass a seed other than the rollout's, or batch
+ *               row i would repeat env i's exploration noise;
+ *   qmin = min(q1, q2) of target's critics on (next_state, a2);
+ *   y = reward + gamma (qmin - alpha logp2) where the row bootstraps, y = reward exactly where not.
+ * bootstrap_truncated = 0 is the reference as written (no bootstrap where end != 0);
+ * bootstrap_truncated = 1 keeps the bootstrap where end == 2.  Reads batch->next_state, reward and
+ * end.  y: device [n]; a2, u2 [n][n_actions], logp2, qmin [n]: optional device outputs, any may be
+ * NULL.  Two launches (the actor, then the critics) with no host synchronisation between them. */
+int  gm_sac_target(gm_sac* target, gm_sac* online, const gm_sac_batch* batch, int n, float gamma, float alpha,
+                   int bootstrap_truncated, uint64_t seed, uint64_t draw, float* y, float* a2, float* u2,
+                   float* logp2, float* qmin);
+
 #ifdef __cplusplus
 }
 #endif

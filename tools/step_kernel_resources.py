@@ -26,7 +26,8 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 SECTIONS = (".text", ".rodata", ".note")
 FUNCS = ("ac_rollout_driver", "replay_record", "ga_sample", "gm_ac_kernel", "gm_ac_gae_kernel", "gm_policy_kernel",
          "gm_td_target_kernel", "gm_replay_sample_kernel", "gm_learn_grad_kernel", "gm_learn_step_kernel",
-         "substep_loop", "reset_env", "driver_actions")
+         "substep_loop", "reset_env", "driver_actions", "sac_rollout_driver", "gs_sample", "gm_sac_actor_kernel",
+         "gm_sac_q_kernel", "gm_sac_push_begin_kernel", "gm_sac_replay_sample_kernel")
 
 
 def tool(name, *args):
@@ -57,7 +58,7 @@ def usage(obj):
                               scratch_bytes_per_lane=int(g("private_segment_fixed_size")), code_bytes=size.get(name))
     funcs = {}
     for f in FUNCS:   # a template's instantiations go by their symbols
-        hits = {s: n for s, n in size.items() if f in s}
+        hits = {s: n for s, n in size.items() if re.search(r"(?<![A-Za-z_])" + re.escape(f), s)}   # (not a longer name's tail)
         funcs.update({f: n for n in hits.values()} if len(hits) == 1 else hits)
     return dict(kernels=kernels, functions=funcs)
 
