@@ -6,9 +6,18 @@
  * amplifies a last-bit difference over a 63-substep env-step.  Both sides therefore use
  * this one implementation, so identical inputs give identical bits: Cody-Waite reduction
  * by pi/2 (33 + 53 bit split; exact for |x| < 2^20) and the fdlibm __kernel_sin /
- * __kernel_cos minimax polynomials (tail term zero), about 1 ulp.  Every operation is a
- * separately rounded IEEE-754 double operation written out explicitly (callers build with
- * FMA contraction off), so the result does not depend on the compiler or the target.
+ * __kernel_cos minimax polynomials (tail term zero).  Every operation is a separately
+ * rounded IEEE-754 double operation written out explicitly (callers build with FMA
+ * contraction off), so the result does not depend on the compiler or the target.
+ *
+ * Accuracy, measured against mpmath for |x| < 2^20 (tests/test_device_primitives.py: the
+ * host build there, the device build tied to it bit for bit): at most 1.3075 ulps (asserted:
+ * 1.5) wherever |result| >= 2^-10 and at most 1.33e-16 absolute (asserted: 2.66e-16)
+ * everywhere.  Next to a non-zero multiple k pi/2 the result that crosses zero is off by
+ * k * 3.5e-27 (pio2_1 + pio2_1t is pi/2 to 86 bits and no third term follows), which is tiny
+ * absolutely and large relatively: about 3e5 ulps already for k <= 8, up to 2.9e-5 of the
+ * result at the multiple below 2^20 that lies closest to a double.  The sign of zero is
+ * not kept: gm_sin(-0.0) is +0.0.
  */
 #ifndef GM_MATH_H
 #define GM_MATH_H
