@@ -26,6 +26,7 @@
 #include "gm_ac.hip"
 #include "gm_ppo_learn.hip"
 #include "gm_sac.hip"
+#include "gm_sac_learn.hip"
 
 // calibration translation unit (gm_calib.hip)
 hipError_t gm_cal_launch_step(int n_seg, int n_envs, hipStream_t st, GmEnvState* states, const gm_model* m,
@@ -2435,6 +2436,7 @@ int64_t gm_sac_struct_size(int which) {
     case 0: return (int64_t)sizeof(gm_sac_replay);
     case 1: return (int64_t)sizeof(gm_sac_batch);
     case 2: return (int64_t)sizeof(gm_sac_opt);
+    case 4: return (int64_t)sizeof(gm_sac_learn_opt);
     default: return -1;
   }
 }
@@ -2720,6 +2722,338 @@ int gm_sac_target(gm_sac* target, gm_sac* online, const gm_sac_batch* batch, int
   hipLaunchKernelGGL(gm_sac_q_kernel, dim3((n + GP_TILE - 1) / GP_TILE), dim3(64), 0, c->stream, batch->next_state,
                      (const float*)a, n, target->d_params.get(), target->net, (float*)nullptr, (float*)nullptr, B);
   HIPCHK(c, hipGetLastError());
+  return GM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- on-device SAC learner
+struct gm_sac_learner {
+  gm_ctx* ctx = nullptr;
+  gm_sac* online = nullptr;
+  gm_sac_learn_opt opt{};
+  GlPlan plan_pi{}, plan_q{};
+  int64_t step_q = 0, step_pi = 0;   // optimiser steps taken
+  int64_t pi_total = 0, q_total = 0; // packed floats of the actor and of one critic
+  DevBuf<float> d_part_q;       // [GL_MAX_TILES][2 q_total] per-tile gradients of [q1 | q2]
+  DevBuf<float> d_part_pi;      // [GL_MAX_TILES][pi_total]
+  DevBuf<float> d_tile_loss;    // [3][GL_MAX_TILES]: q1, q2, pi
+  DevBuf<float> d_grad, d_m, d_v, d_vmax;   // [blob], packed order: both optimisers' ranges
+  DevBuf<float> d_loss;         // [2] loss_q, loss_pi of the held gradients
+  DevBuf<float> d_spill_q, d_spill_pi;      // the gradient kernels' rows where they do not fit LDS
+  // gm_sac_learner_train's batch and backup
+  DevBuf<float> d_state, d_action, d_next, d_reward, d_y;
+  DevBuf<int32_t> d_index;
+  DevBuf<uint8_t> d_end;
+};
+
+static gm_dqn_opt sac_learner_dqn_opt(const gm_sac_learn_opt& o) {   // (learner_opt's input; SAC has no clamp)
+  return gm_dqn_opt{o.optimiser, o.amsgrad, GM_LOSS_MSE, 0, o.lr, o.beta1, o.beta2, o.eps, o.weight_decay, 0.0};
+}
+// One launch of gm_learn_step_kernel over one optimiser's range of the blob: the critics'
+// [q1 | q2] or the actor's [pi].  target: the handle whose same range is polyak-updated, or NULL.
+static hipError_t sac_launch_step(gm_sac_learner* l, bool critics, bool sum, bool step, gm_sac* target, float tau, int n,
+                                  float* loss_out) {
+  gm_ctx* c = l->ctx;
+  const long long off = critics ? l->online->net.q1_off : 0;
+  GlStepArgs a{};
+  a.do_sum = sum;
+  a.do_step = step;
+  a.do_soft = target != nullptr;
+  a.n_tiles = (n + GP_TILE - 1) / GP_TILE;
+  a.n = n;
+  a.total = critics ? 2 * (long long)l->q_total : (long long)l->pi_total;
+  a.partials = critics ? l->d_part_q.get() : l->d_part_pi.get();
+  a.tile_loss = l->d_tile_loss.get() + (critics ? 0 : 2 * GL_MAX_TILES);
+  a.tile_loss2 = critics ? l->d_tile_loss.get() + GL_MAX_TILES : nullptr;
+  a.grad = l->d_grad.get() + off;
+  a.loss = l->d_loss.get() + (critics ? 0 : 1);
+  a.loss_out = loss_out;
+  a.p = l->online->d_params.get() + off;
+  a.m = l->d_m.get() + off;
+  a.v = l->d_v.get() + off;
+  a.vmax = l->d_vmax.get() + off;
+  a.target = target ? target->d_params.get() + off : nullptr;
+  a.tau = tau;
+  a.opt = learner_opt(sac_learner_dqn_opt(l->opt), std::max<int64_t>(critics ? l->step_q : l->step_pi, 1));
+  const int threads = 256;
+  hipLaunchKernelGGL(gm_learn_step_kernel, dim3((unsigned)((a.total + threads - 1) / threads)), dim3(threads), 0,
+                     c->stream, a);
+  return hipGetLastError();
+}
+static hipError_t sac_launch_grad_q(gm_sac_learner* l, const float* state, const float* action, const float* y, int n) {
+  gm_sac* p = l->online;
+  GslQArgs a{};
+  a.state = state;
+  a.action = action;
+  a.y = y;
+  a.n = n;
+  a.params = p->d_params;
+  a.net = p->net;
+  a.plan = l->plan_q;
+  a.spill = l->d_spill_q;
+  a.partials = l->d_part_q;
+  a.q_total = (long long)l->q_total;
+  a.tile_loss = l->d_tile_loss;
+  const dim3 grid((n + GP_TILE - 1) / GP_TILE, 2);
+  if (p->net.act == GP_ACT_TANH) hipLaunchKernelGGL(gm_sac_grad_q_kernel<GP_ACT_TANH>, grid, dim3(64), 0, l->ctx->stream, a);
+  else hipLaunchKernelGGL(gm_sac_grad_q_kernel<GP_ACT_RELU>, grid, dim3(64), 0, l->ctx->stream, a);
+  return hipGetLastError();
+}
+static hipError_t sac_launch_grad_pi(gm_sac_learner* l, const float* state, int n, float alpha, uint64_t seed,
+                                     uint64_t draw, float* z, float* u, float* act, float* logp, float* q1, float* q2) {
+  gm_sac* p = l->online;
+  GslPiArgs a{};
+  a.state = state;
+  a.n = n;
+  a.params = p->d_params;
+  a.net = p->net;
+  a.plan_pi = l->plan_pi;
+  a.plan_q = l->plan_q;
+  a.spill = l->d_spill_pi;
+  a.partials = l->d_part_pi;
+  a.pi_total = (long long)l->pi_total;
+  a.tile_loss = l->d_tile_loss.get() + 2 * GL_MAX_TILES;
+  a.alpha = alpha;
+  a.seed = seed;
+  a.draw = draw;
+  a.z = z; a.u = u; a.a = act; a.logp = logp; a.q1 = q1; a.q2 = q2;
+  const dim3 grid((n + GP_TILE - 1) / GP_TILE);
+  if (p->net.act == GP_ACT_TANH) hipLaunchKernelGGL(gm_sac_grad_pi_kernel<GP_ACT_TANH>, grid, dim3(64), 0, l->ctx->stream, a);
+  else hipLaunchKernelGGL(gm_sac_grad_pi_kernel<GP_ACT_RELU>, grid, dim3(64), 0, l->ctx->stream, a);
+  return hipGetLastError();
+}
+static bool sac_same_sizes(const gm_sac* a, const gm_sac* b) { return a->pisz == b->pisz && a->qsz == b->qsz; }
+// packed device array [blob] -> flat host array (out) through one copy
+static int sac_learner_unpack(gm_ctx* c, const gm_sac* p, const float* d_packed, float* out) {
+  std::vector<float> packed((size_t)p->total);
+  const int rc = read_back(c, packed.data(), d_packed, sizeof(float) * (size_t)p->total);
+  if (rc != GM_OK) return rc;
+  gsl_unpack(p->net, packed.data(), out);
+  return GM_OK;
+}
+static int sac_batch_check(gm_ctx* c, const char* what, int n) {
+  if (n < 1) return fail(c, GM_E_ARG, std::string(what) + ": n < 1");
+  if (n > GL_MAX_BATCH)
+    return fail(c, GM_E_ARG, std::string(what) + ": " + std::to_string(n) + " rows, the learner holds " +
+                                 std::to_string(GL_MAX_BATCH));
+  return GM_OK;
+}
+
+extern "C" {
+
+void gm_sac_learn_opt_default(gm_sac_learn_opt* out) {
+  if (!out) return;
+  *out = gm_sac_learn_opt{GM_OPT_ADAM, 0, 1e-4, 0.9, 0.999, 1e-8, 0.0};
+}
+
+int gm_sac_learner_create(gm_sac* online, const gm_sac_learn_opt* opt, gm_sac_learner** out) {
+  if (!online || !online->ctx || !out) return GM_E_ARG;
+  gm_ctx* c = online->ctx;
+  gm_sac_learn_opt o;
+  gm_sac_learn_opt_default(&o);
+  if (opt) o = *opt;
+  if (o.optimiser != GM_OPT_ADAM && o.optimiser != GM_OPT_ADAMW)
+    return fail(c, GM_E_ARG, "gm_sac_learner_create: optimiser must be GM_OPT_ADAM / GM_OPT_ADAMW");
+  if (!(o.lr >= 0) || !(o.beta1 >= 0 && o.beta1 < 1) || !(o.beta2 >= 0 && o.beta2 < 1) || !(o.eps >= 0) || !(o.weight_decay >= 0))
+    return fail(c, GM_E_ARG, "gm_sac_learner_create: lr, eps, weight_decay >= 0 and betas in [0, 1) expected");
+  HIPCHK(c, hipSetDevice(c->device));
+  gm_sac_learner* l = new gm_sac_learner;
+  l->ctx = c;
+  l->online = online;
+  l->opt = o;
+  l->plan_pi = gl_plan(online->net.pi);
+  l->plan_q = gl_plan(online->net.q);
+  l->pi_total = online->net.q1_off;
+  l->q_total = online->net.q2_off - online->net.q1_off;
+  const size_t total = (size_t)online->total, n_obs = (size_t)c->cfg.n_obs, na = (size_t)online->net.n_act;
+  const long long pi_rows = gsl_pi_rows(l->plan_pi, l->plan_q);
+  hipError_t e = l->d_part_q.alloc(2 * (size_t)l->q_total * GL_MAX_TILES);
+  if (e == hipSuccess) e = l->d_part_pi.alloc((size_t)l->pi_total * GL_MAX_TILES);
+  if (e == hipSuccess) e = l->d_tile_loss.alloc(3 * GL_MAX_TILES);
+  if (e == hipSuccess) e = l->d_grad.alloc(total);
+  if (e == hipSuccess) e = l->d_m.alloc(total);
+  if (e == hipSuccess) e = l->d_v.alloc(total);
+  if (e == hipSuccess) e = l->d_vmax.alloc(total);
+  if (e == hipSuccess) e = l->d_loss.alloc(2);
+  if (e == hipSuccess) e = l->d_spill_q.alloc(l->plan_q.total > GL_ARENA ? (size_t)l->plan_q.total * 2 * GL_MAX_TILES : 1);
+  if (e == hipSuccess) e = l->d_spill_pi.alloc(pi_rows > GL_ARENA ? (size_t)pi_rows * GL_MAX_TILES : 1);
+  if (e == hipSuccess) e = l->d_state.alloc(n_obs * GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_action.alloc(na * GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_next.alloc(n_obs * GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_reward.alloc(GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_y.alloc(GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_index.alloc(GL_MAX_BATCH);
+  if (e == hipSuccess) e = l->d_end.alloc(GL_MAX_BATCH);
+  for (float* z : {l->d_grad.get(), l->d_m.get(), l->d_v.get(), l->d_vmax.get()})
+    if (e == hipSuccess) e = hipMemsetAsync(z, 0, sizeof(float) * total, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(l->d_loss, 0, 2 * sizeof(float), c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    gm_sac_learner_destroy(l);
+    return fail(c, GM_E_HIP, std::string("gm_sac_learner_create: ") + hipGetErrorString(e));
+  }
+  *out = l;
+  return GM_OK;
+}
+
+void gm_sac_learner_destroy(gm_sac_learner* l) {
+  if (!l) return;
+  if (l->ctx) {
+    (void)hipSetDevice(l->ctx->device);
+    (void)hipStreamSynchronize(l->ctx->stream);   // the stream may still use the learner's buffers
+  }
+  delete l;
+}
+
+int gm_sac_learner_grad_q(gm_sac_learner* l, const gm_sac_batch* batch, const float* y, int n) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  const int rc = sac_batch_check(c, "gm_sac_learner_grad_q", n);
+  if (rc != GM_OK) return rc;
+  if (!batch || !batch->state || !batch->action || !y)
+    return fail(c, GM_E_ARG, "gm_sac_learner_grad_q: incomplete batch (state, action) or no y");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, sac_launch_grad_q(l, batch->state, batch->action, y, n));
+  HIPCHK(c, sac_launch_step(l, true, true, false, nullptr, 0.0f, n, nullptr));
+  return GM_OK;
+}
+
+int gm_sac_learner_grad_pi(gm_sac_learner* l, const gm_sac_batch* batch, int n, float alpha, uint64_t seed, uint64_t draw,
+                           float* z, float* u, float* a, float* logp, float* q1, float* q2) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  const int rc = sac_batch_check(c, "gm_sac_learner_grad_pi", n);
+  if (rc != GM_OK) return rc;
+  if (!batch || !batch->state) return fail(c, GM_E_ARG, "gm_sac_learner_grad_pi: incomplete batch (state)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, sac_launch_grad_pi(l, batch->state, n, alpha, seed, draw, z, u, a, logp, q1, q2));
+  HIPCHK(c, sac_launch_step(l, false, true, false, nullptr, 0.0f, n, nullptr));
+  return GM_OK;
+}
+
+int gm_sac_learner_step_q(gm_sac_learner* l) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  l->step_q++;
+  HIPCHK(c, sac_launch_step(l, true, false, true, nullptr, 0.0f, 1, nullptr));
+  return GM_OK;
+}
+
+int gm_sac_learner_step_pi(gm_sac_learner* l) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  l->step_pi++;
+  HIPCHK(c, sac_launch_step(l, false, false, true, nullptr, 0.0f, 1, nullptr));
+  return GM_OK;
+}
+
+int gm_sac_soft_update(gm_sac* target, gm_sac* online, float tau) {
+  if (!target || !target->ctx || !online) return GM_E_ARG;
+  gm_ctx* c = target->ctx;
+  if (online->ctx != c) return fail(c, GM_E_ARG, "gm_sac_soft_update: the two handles belong to different contexts");
+  if (!sac_same_sizes(target, online)) return fail(c, GM_E_ARG, "gm_sac_soft_update: the two handles have different network sizes");
+  if (!(tau >= 0.0f && tau <= 1.0f)) return fail(c, GM_E_ARG, "gm_sac_soft_update: tau in [0, 1] expected");
+  HIPCHK(c, hipSetDevice(c->device));
+  GlStepArgs a{};
+  a.do_soft = 1;
+  a.total = (long long)online->total;
+  a.p = online->d_params;
+  a.target = target->d_params;
+  a.tau = tau;
+  const int threads = 256;
+  hipLaunchKernelGGL(gm_learn_step_kernel, dim3((unsigned)((a.total + threads - 1) / threads)), dim3(threads), 0,
+                     c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return GM_OK;
+}
+
+int gm_sac_learner_read(gm_sac_learner* l, float* grad_flat, float* loss_q, float* loss_pi) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (grad_flat) {
+    const int rc = sac_learner_unpack(c, l->online, l->d_grad, grad_flat);
+    if (rc != GM_OK) return rc;
+  }
+  float both[2];
+  const int rc = read_back(c, both, l->d_loss, sizeof(both));
+  if (rc != GM_OK) return rc;
+  if (loss_q) *loss_q = both[0];
+  if (loss_pi) *loss_pi = both[1];
+  return GM_OK;
+}
+
+int gm_sac_learner_get_state(gm_sac_learner* l, int64_t* steps, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (steps) { steps[0] = l->step_q; steps[1] = l->step_pi; }
+  const float* src[3] = {l->d_m, l->d_v, l->d_vmax};
+  float* dst[3] = {exp_avg, exp_avg_sq, max_exp_avg_sq};
+  for (int i = 0; i < 3; i++)
+    if (dst[i]) {
+      const int rc = sac_learner_unpack(c, l->online, src[i], dst[i]);
+      if (rc != GM_OK) return rc;
+    }
+  return GM_OK;
+}
+
+int gm_sac_learner_set_state(gm_sac_learner* l, const int64_t* steps, const float* exp_avg, const float* exp_avg_sq,
+                             const float* max_exp_avg_sq) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  if (steps && (steps[0] < 0 || steps[1] < 0)) return fail(c, GM_E_ARG, "gm_sac_learner_set_state: negative step");
+  HIPCHK(c, hipSetDevice(c->device));
+  const float* src[3] = {exp_avg, exp_avg_sq, max_exp_avg_sq};
+  float* dst[3] = {l->d_m, l->d_v, l->d_vmax};
+  gm_sac* p = l->online;
+  std::vector<float> packed((size_t)p->total);
+  for (int i = 0; i < 3; i++)
+    if (src[i]) {
+      gsl_pack(p->net, p->total, src[i], packed.data());
+      const int rc = stage_upload(c, dst[i], packed.data(), sizeof(float) * (size_t)p->total);
+      if (rc != GM_OK) return rc;
+    }
+  if (steps) { l->step_q = steps[0]; l->step_pi = steps[1]; }
+  return GM_OK;
+}
+
+int gm_sac_learner_train(gm_sac_learner* l, gm_sac* target, const gm_sac_replay* replay, int64_t size, int batch,
+                         uint64_t seed, uint64_t noise_seed, uint64_t draw0, int n_updates, float gamma, float alpha,
+                         int bootstrap_truncated, float tau, float* losses) {
+  if (!l || !l->ctx) return GM_E_ARG;
+  gm_ctx* c = l->ctx;
+  gm_sac* online = l->online;
+  if (!target) return fail(c, GM_E_ARG, "gm_sac_learner_train: no target handle");
+  if (target->ctx != c) return fail(c, GM_E_ARG, "gm_sac_learner_train: the two handles belong to different contexts");
+  if (!sac_same_sizes(target, online)) return fail(c, GM_E_ARG, "gm_sac_learner_train: the two handles have different network sizes");
+  if (n_updates < 1) return fail(c, GM_E_ARG, "gm_sac_learner_train: n_updates < 1");
+  if (batch > GL_MAX_BATCH)
+    return fail(c, GM_E_ARG, "gm_sac_learner_train: batch " + std::to_string(batch) + ", the learner holds " +
+                                 std::to_string(GL_MAX_BATCH));
+  if (tau > 0.0f && (target == online || !(tau <= 1.0f)))
+    return fail(c, GM_E_ARG, "gm_sac_learner_train: a polyak update needs a target handle of its own and tau <= 1");
+  gm_sac* soft = tau > 0.0f ? target : nullptr;
+  const gm_sac_batch b{l->d_state, l->d_action, l->d_next, l->d_reward, l->d_end, l->d_index};
+  for (int u = 0; u < n_updates; u++) {
+    const uint64_t d = draw0 + (uint64_t)u;
+    int rc = gm_sac_replay_sample(c, replay, size, batch, seed, d, &b);   // (validates replay, size, batch)
+    if (rc == GM_OK)
+      rc = gm_sac_target(target, online, &b, batch, gamma, alpha, bootstrap_truncated, noise_seed, 2 * d, l->d_y, nullptr,
+                         nullptr, nullptr, nullptr);
+    if (rc != GM_OK) return rc;
+    HIPCHK(c, sac_launch_grad_q(l, l->d_state, l->d_action, l->d_y, batch));
+    l->step_q++;
+    // (each range's polyak update rides in its step launch: elementwise what gm_sac_soft_update does after both steps)
+    HIPCHK(c, sac_launch_step(l, true, true, true, soft, tau, batch, losses ? losses + 2 * u : nullptr));
+    HIPCHK(c, sac_launch_grad_pi(l, l->d_state, batch, alpha, noise_seed, 2 * d + 1, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr));
+    l->step_pi++;
+    HIPCHK(c, sac_launch_step(l, false, true, true, soft, tau, batch, losses ? losses + 2 * u + 1 : nullptr));
+  }
   return GM_OK;
 }
 

@@ -3,7 +3,8 @@
 // order, steps Adam / AdamW and soft-updates a target net (gm_learn_step_kernel).  Shared rules
 // and the row plan are gm_learn.h's; the forward is gm_policy_net.h's chain, kept layer by layer.
 // The layer-wise forward and backward of one tile (gl_forward_rows, gl_backward_rows) and the step
-// kernel are also the PPO learner's (gm_ppo_learn.hip), which passes tanh where this file passes ReLU.
+// kernel are also the PPO learner's (gm_ppo_learn.hip), which passes tanh where this file passes ReLU,
+// and the SAC learner's (gm_sac_learn.hip), which also walks gl_delta_prev alone down its frozen critics.
 //
 // Kernels are ordered by the context's stream and, inside a kernel, by workgroup barriers only:
 // no workgroup waits for another one, and no float atomic is used, so two runs give the same bits.
@@ -12,24 +13,12 @@
 
 #define GL_AHEAD 8   // k steps whose operands gl_forward_rows / gl_backward_rows load ahead of the MFMA chain
 
-// One tile's forward with every layer's rows kept: gp_forward_tile's arithmetic (same MFMA chain,
-// k order, bias placement; hidden layers through gp_activate(code), a caller's literal) on rows
-// e0 .. e0 + 15 of x[n][width 0], the post-activation rows of every layer left under the plan L
-// from `base` -- LDS when the plan fits GL_ARENA, else the caller's global spill rows (written
-// and read by this wave only, between barriers).  Rows >= n and padded columns are 0.
-__device__ __forceinline__ void gl_forward_rows(const float* __restrict__ x, size_t e0, size_t n,
-                                                const float* __restrict__ params, const GpNet& P, const GlPlan& L,
-                                                float* base, int code, int lane) {
+// The layers of gl_forward_rows on input rows already under the plan (a[0]: [16][kpad[0]], 0 where
+// a row or a column is padding, written before a barrier): the only MFMA loop of the learners'
+// forwards.  The SAC learner (gm_sac_learn.hip) assembles [state | action] rows there itself.
+__device__ __forceinline__ void gl_layers_rows(const float* __restrict__ params, const GpNet& P, const GlPlan& L,
+                                               float* base, int code, int lane) {
   const int g = lane >> 4, nn = lane & 15;
-  {
-    const int n_obs = P.width[0], k0 = P.kpad[0], S0 = L.a_stride[0];
-    float* A0 = base + L.a_off[0];
-    for (int i = lane; i < GP_TILE * k0; i += 64) {
-      const int r = i / k0, k = i - r * k0;
-      A0[r * S0 + k] = (e0 + r < n && k < n_obs) ? x[(e0 + r) * n_obs + k] : 0.0f;
-    }
-  }
-  __syncthreads();
   for (int l = 0; l < P.n_layers; l++) {
     const float* __restrict__ W = params + P.woff[l];
     const float* __restrict__ Bv = params + P.boff[l];
@@ -69,9 +58,62 @@ __device__ __forceinline__ void gl_forward_rows(const float* __restrict__ x, siz
   }
 }
 
+// One tile's forward with every layer's rows kept: gp_forward_tile's arithmetic (same MFMA chain,
+// k order, bias placement; hidden layers through gp_activate(code), a caller's literal) on rows
+// e0 .. e0 + 15 of x[n][width 0], the post-activation rows of every layer left under the plan L
+// from `base` -- LDS when the plan fits GL_ARENA, else the caller's global spill rows (written
+// and read by this wave only, between barriers).  Rows >= n and padded columns are 0.
+__device__ __forceinline__ void gl_forward_rows(const float* __restrict__ x, size_t e0, size_t n,
+                                                const float* __restrict__ params, const GpNet& P, const GlPlan& L,
+                                                float* base, int code, int lane) {
+  {
+    const int n_obs = P.width[0], k0 = P.kpad[0], S0 = L.a_stride[0];
+    float* A0 = base + L.a_off[0];
+    for (int i = lane; i < GP_TILE * k0; i += 64) {
+      const int r = i / k0, k = i - r * k0;
+      A0[r * S0 + k] = (e0 + r < n && k < n_obs) ? x[(e0 + r) * n_obs + k] : 0.0f;
+    }
+  }
+  __syncthreads();
+  gl_layers_rows(params, P, L, base, code, lane);
+}
+
 // dL/dz of a hidden layer from dL/da (c) and the stored activation a: ReLU's [a > 0], tanh's 1 - a^2
 __device__ __forceinline__ float gl_act_grad(float c, float a, int code) {
   return code == GP_ACT_TANH ? c * (1.0f - a * a) : (a > 0.0f ? c : 0.0f);
+}
+
+// The product that carries deltas down through a layer's packed weights W ([.][kpad] in B-fragment
+// order): store(i, k, sum_j D[i][j] W[j][k]) for the 16 rows i and every k of the 16-wide column
+// blocks kb_lo, kb_lo + 16, ... < kb_hi (0 for k >= kpad), j running over [0, jmax) (the deltas of
+// padded columns are 0).  MFMA with M = the 16 rows, N = 16 k's, reduction over j in steps of 4, W
+// gathered from the B-fragment order (4 consecutive floats per (k, j quad)); lane (g, nn) stores
+// rows 4 g .. 4 g + 3 of column kb + nn, the same entries on every call.  gl_backward_rows' step
+// between two layers; the SAC learner's way down a frozen critic to its input (gm_sac_learn.hip).
+template <class Store>
+__device__ __forceinline__ void gl_delta_prev(const float* __restrict__ W, int kpad, int jmax, const float* D, int Sd,
+                                              int kb_lo, int kb_hi, int lane, Store store) {
+  const int g = lane >> 4, nn = lane & 15;
+  const int ksteps = kpad >> 2;
+  for (int kb = kb_lo; kb < kb_hi; kb += 16) {
+    gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int k = kb + nn;
+    for (int q0 = 0; q0 < jmax; q0 += 4 * GL_AHEAD) {     // (operands ahead of their MFMAs, as in the forward)
+      const int m = min(GL_AHEAD, (jmax - q0) >> 2);
+      float a[GL_AHEAD], b[GL_AHEAD];
+#pragma unroll
+      for (int u = 0; u < GL_AHEAD; u++) {
+        const int j = q0 + 4 * u + g;
+        a[u] = u < m ? D[nn * Sd + j] : 0.0f;
+        b[u] = (u < m && k < kpad) ? W[((size_t)(j >> 4) * ksteps + (k >> 2)) * 64 + (k & 3) * 16 + (j & 15)] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < GL_AHEAD; u++)
+        if (u < m) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u], c, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) store(4 * g + r, k, c[r]);
+  }
 }
 
 // One tile's backward through the layers, from the deltas of the last layer's outputs in the
@@ -86,9 +128,7 @@ __device__ __forceinline__ float gl_act_grad(float c, float a, int code) {
 //                                       so register r of lane (g, n) is packed element
 //                                       (tile t, k step s0 + r, lane 16 g + n): coalesced stores;
 //   db[j]    = sum_i D[i][j]            in row order;
-//   Dprev[i][k] = act'(A[i][k]) sum_j D[i][j] W[j][k]   MFMA with M = the 16 rows, N = 16 k's,
-//                                       reduction over j in steps of 4, W gathered from the
-//                                       B-fragment order (4 consecutive floats per (k, j quad)).
+//   Dprev[i][k] = act'(A[i][k]) sum_j D[i][j] W[j][k]   gl_delta_prev.
 __device__ __forceinline__ void gl_backward_rows(const float* __restrict__ params, const GpNet& P, const GlPlan& L,
                                                  float* base, float* __restrict__ part, int code, bool add, int lane) {
   const int g = lane >> 4, nn = lane & 15;
@@ -131,30 +171,8 @@ __device__ __forceinline__ void gl_backward_rows(const float* __restrict__ param
     if (l == 0) break;
     // the deltas of the layer below, through W and the activation that made A
     float* Dn = base + L.d_off[cur ^ 1];
-    const int wprev = P.tiles[l - 1] * 16;
-    const int jmax = (P.width[l + 1] + 3) & ~3;    // (the deltas of padded columns are 0)
-    for (int kb = 0; kb < wprev; kb += 16) {
-      gp_f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
-      const int k = kb + nn;
-      for (int q0 = 0; q0 < jmax; q0 += 4 * GL_AHEAD) {     // (operands ahead of their MFMAs, as in the forward)
-        const int m = min(GL_AHEAD, (jmax - q0) >> 2);
-        float a[GL_AHEAD], b[GL_AHEAD];
-#pragma unroll
-        for (int u = 0; u < GL_AHEAD; u++) {
-          const int j = q0 + 4 * u + g;
-          a[u] = u < m ? D[nn * Sd + j] : 0.0f;
-          b[u] = (u < m && k < kpad) ? W[((size_t)(j >> 4) * ksteps + (k >> 2)) * 64 + (k & 3) * 16 + (j & 15)] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < GL_AHEAD; u++)
-          if (u < m) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u], c, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int i = 4 * g + r;
-        Dn[i * Sd + k] = gl_act_grad(c[r], A[i * Sa + k], code);
-      }
-    }
+    gl_delta_prev(W, kpad, (P.width[l + 1] + 3) & ~3, D, Sd, 0, P.tiles[l - 1] * 16, lane,
+                  [&](int i, int k, float c) { Dn[i * Sd + k] = gl_act_grad(c, A[i * Sa + k], code); });
     __syncthreads();
     cur ^= 1;
   }
@@ -235,6 +253,7 @@ struct GlStepArgs {
   long long total;
   const float* partials;
   const float* tile_loss;
+  const float* tile_loss2;   // NULL, or a second loss's per-tile sums: the loss is the sum of the two means (SAC's loss_q)
   float* grad;
   float* loss;           // [1]
   float* loss_out;       // [1] or NULL: a second copy (gm_learner_train's losses[u])
@@ -262,6 +281,11 @@ __global__ __launch_bounds__(256) void gm_learn_step_kernel(GlStepArgs a) {
       float s = 0.0f;
       for (int t = 0; t < a.n_tiles; t++) s += a.tile_loss[t];
       s = s / (float)a.n;
+      if (a.tile_loss2) {
+        float s2 = 0.0f;
+        for (int t = 0; t < a.n_tiles; t++) s2 += a.tile_loss2[t];
+        s = s + s2 / (float)a.n;
+      }
       a.loss[0] = s;
       if (a.loss_out) a.loss_out[0] = s;
     }

@@ -198,6 +198,15 @@ class SacBatch(C.Structure):
                 ("end", C.c_void_p), ("index", C.c_void_p)]
 
 
+class SacLearnOpt(C.Structure):
+    """gm_sac_learn_opt (include/gripper_mi355x.h): the SAC learner's optimiser options."""
+    _fields_ = [("optimiser", C.c_int32), ("amsgrad", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 SAC_MEAN, SAC_SAMPLE, SAC_RANDOM = 0, 1, 2
 ACT_RELU, ACT_TANH = 0, 1
 
@@ -261,8 +270,12 @@ def load_library(path: str | None = None):
             continue   # an older developer build without this struct
         if n != C.sizeof(cls):
             raise ImportError(f"struct layout mismatch for {cls.__name__}: C {n} vs ctypes {C.sizeof(cls)}")
-    for which, cls in {0: SacReplay, 1: SacBatch, 2: SacOpt}.items():
-        if getattr(lib, "gm_sac_struct_size", None) is not None and lib.gm_sac_struct_size(which) != C.sizeof(cls):
+    for which, cls in {0: SacReplay, 1: SacBatch, 2: SacOpt, 4: SacLearnOpt}.items():
+        if getattr(lib, "gm_sac_struct_size", None) is None:
+            continue
+        if lib.gm_sac_struct_size(which) < 0 and os.environ.get("GM_LIB"):
+            continue   # an older developer build without this struct
+        if lib.gm_sac_struct_size(which) != C.sizeof(cls):
             raise ImportError(f"struct layout mismatch for {cls.__name__}: C {lib.gm_sac_struct_size(which)} "
                               f"vs ctypes {C.sizeof(cls)}")
     if path is None:
@@ -404,6 +417,19 @@ def _declare(lib):
         "gm_sac_replay_sample": (i32, [vp, vp, C.c_int64, i32, C.c_uint64, C.c_uint64, vp]),
         "gm_sac_q": (i32, [vp, vp, vp, i32, vp, vp]),
         "gm_sac_target": (i32, [vp, vp, vp, i32, C.c_float, C.c_float, i32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]),
+        "gm_sac_learn_opt_default": (None, [vp]),
+        "gm_sac_learner_create": (i32, [vp, vp, C.POINTER(vp)]),
+        "gm_sac_learner_destroy": (None, [vp]),
+        "gm_sac_learner_grad_q": (i32, [vp, vp, vp, i32]),
+        "gm_sac_learner_grad_pi": (i32, [vp, vp, i32, C.c_float, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+        "gm_sac_learner_step_q": (i32, [vp]),
+        "gm_sac_learner_step_pi": (i32, [vp]),
+        "gm_sac_soft_update": (i32, [vp, vp, C.c_float]),
+        "gm_sac_learner_read": (i32, [vp, f32p, f32p, f32p]),
+        "gm_sac_learner_get_state": (i32, [vp, C.POINTER(C.c_int64), f32p, f32p, f32p]),
+        "gm_sac_learner_set_state": (i32, [vp, C.POINTER(C.c_int64), f32p, f32p, f32p]),
+        "gm_sac_learner_train": (i32, [vp, vp, vp, C.c_int64, i32, C.c_uint64, C.c_uint64, C.c_uint64, i32, C.c_float,
+                                       C.c_float, i32, C.c_float, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -1,7 +1,7 @@
-"""On-device SAC data collection for the batched env: the squashed Gaussian actor, a replay
-memory with float action rows, the twin critics and the soft Bellman backup.
+"""On-device SAC for the batched env: the squashed Gaussian actor, a replay memory with float
+action rows, the twin critics, the soft Bellman backup and the learner.
 
-Mirrors the collection side of the reference's soft actor-critic (rl/agents/ActorCritic.py):
+Mirrors the reference's soft actor-critic (rl/agents/ActorCritic.py):
   - SquashedGaussianMLPActor: mlp([n_obs, *hidden], act, act), then mu_layer and log_std_layer;
     log_std clamped to [-20, 2]; u = mu + std z (or mu); logp = Normal.log_prob(u).sum() -
     sum(2 (log 2 - u - softplus(-2 u))); a = action_limit tanh(u);
@@ -10,9 +10,9 @@ Mirrors the collection side of the reference's soft actor-critic (rl/agents/Acto
   - Agent_SAC.update_step's push of (state, action, next_state, reward, terminal) as
     ActionReplayBuffer, filled by DeviceSAC.push_begin / push_end around an env-step or inside the
     fused launch (rollout(replay=buf));
-  - compute_loss_q's backup, under no_grad, as DeviceSAC.target.
-The learner (the backward of loss_q and loss_pi, the two optimisers, the polyak update) is not
-built; set_params() takes weights that were trained elsewhere.
+  - compute_loss_q's backup, under no_grad, as DeviceSAC.target;
+  - Agent_SAC.optimise_model (the backward of loss_q and loss_pi, q_optimiser and pi_optimiser,
+    the polyak update) as DeviceSACLearner, in place on the device weights the rollout reads.
 """
 from __future__ import annotations
 
@@ -20,7 +20,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import load_library, SacOpt, SacReplay, SacBatch, SAC_MEAN, SAC_SAMPLE, SAC_RANDOM, ACT_RELU, ACT_TANH
+from ._lib import (load_library, SacOpt, SacReplay, SacBatch, SacLearnOpt, SAC_MEAN, SAC_SAMPLE, SAC_RANDOM, ACT_RELU,
+                   ACT_TANH, OPT_ADAM, OPT_ADAMW)
 from .policy import as_f32, linear_init, state_dict_net
 from .ppo import _counters, normal_draws        # noqa: F401  (normal_draws: the sampler's z, re-exported)
 
@@ -44,6 +45,36 @@ def sac_options(**options) -> dict:
     if unknown:
         raise ValueError(f"incorrect key: {', '.join(unknown)}")
     return dict(SAC_DEFAULTS, **options)
+
+
+_OPTIMISERS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW}
+LEARNER_MAX_BATCH = 256     # GM_LEARNER_MAX_BATCH
+
+
+def sac_opt(eps: float = 1e-8, weight_decay=None, amsgrad=None, **options) -> SacLearnOpt:
+    """Agent_SAC.Parameters (by their own names, as sac_options takes them) as Agent_SAC.init hands
+    them to torch, as a gm_sac_learn_opt: "adam" is torch.optim.Adam(lr, betas) -- weight_decay 0,
+    no amsgrad; "adamW" is torch.optim.AdamW(lr, betas, amsgrad=True) -- weight_decay 0.01, torch's
+    default.  weight_decay / amsgrad, when given, override that.  Unknown names raise as
+    Parameters.update does; RMSprop is not on the device.  No GPU needed."""
+    o = sac_options(**options)
+    name = str(o["optimiser"]).lower()
+    if name not in _OPTIMISERS:
+        raise ValueError(f"optimiser {o['optimiser']!r}: 'adam' or 'adamW' expected (RMSprop is not on the device)")
+    out = SacLearnOpt()
+    out.optimiser = _OPTIMISERS[name]
+    out.amsgrad = int(name == "adamw" if amsgrad is None else bool(amsgrad))
+    out.lr, out.beta1, out.beta2, out.eps = (float(o["learning_rate"]), float(o["adam_beta1"]), float(o["adam_beta2"]),
+                                             float(eps))
+    out.weight_decay = float((0.01 if name == "adamw" else 0.0) if weight_decay is None else weight_decay)
+    return out
+
+
+def sac_opt_default() -> SacLearnOpt:
+    """gm_sac_learn_opt_default: the library's own defaults (equal to sac_opt()'s)."""
+    o = SacLearnOpt()
+    load_library().gm_sac_learn_opt_default(C.byref(o))
+    return o
 
 
 def _mode(mode) -> int:
@@ -386,10 +417,145 @@ class DeviceSAC:
         torch.cuda.synchronize(dev)     # the env's stream, before torch reads the results
         return (y, dbg) if debug else y
 
+    def soft_update(self, online: "DeviceSAC", tau: float):
+        """self <- tau online + (1 - tau) self over all three nets, on the device (optimise_model's
+        polyak update, self being mlp_ac_targ); tau = 1 copies online bit for bit."""
+        self._check(self.lib.gm_sac_soft_update(self._p, online._p, C.c_float(tau)), "gm_sac_soft_update")
+
     def close(self):
         if self._p:
             self.lib.gm_sac_destroy(self._p)
             self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceSACLearner:
+    """Agent_SAC.optimise_model on the device weights of `sac` (mlp_ac) and `target` (mlp_ac_targ):
+    loss_q's backward and q_optimiser on [q1 | q2], loss_pi's backward through the frozen critics
+    and pi_optimiser on [pi], the polyak update of all three nets.  Options are Agent_SAC.Parameters'
+    names (sac_opt reads learning_rate, optimiser, adam_beta1, adam_beta2; train() reads gamma,
+    alpha, batch_size and soft_target_tau) plus bootstrap_truncated (DeviceSAC.target's) and
+    sac_opt's eps / weight_decay / amsgrad."""
+
+    def __init__(self, sac: DeviceSAC, target: DeviceSAC | None = None, bootstrap_truncated: bool = False,
+                 eps: float = 1e-8, weight_decay=None, amsgrad=None, **options):
+        self.sac, self.target = sac, target
+        self.env, self.lib = sac.env, sac.lib
+        self.options = sac_options(**options)
+        self.bootstrap_truncated = bool(bootstrap_truncated)
+        self.opt = sac_opt(eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **options)
+        self._l = C.c_void_p()
+        self._check(self.lib.gm_sac_learner_create(sac._p, C.byref(self.opt), C.byref(self._l)), "gm_sac_learner_create")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(self.lib.gm_last_error(self.env.ctx).decode() or f"{what} failed ({rc})")
+
+    def grad_q(self, batch: dict, y):
+        """loss_q.backward() for a sampled batch (state and action are read) and its backup y (a
+        device tensor [n], DeviceSAC.target's): leaves the raw gradient of [q1 | q2] and loss_q on
+        the device."""
+        import torch
+        n = int(y.shape[0])
+        b = _batch_struct(batch)
+        torch.cuda.synchronize(y.device)     # torch-side writes to the batch and y
+        self._check(self.lib.gm_sac_learner_grad_q(self._l, C.byref(b), C.c_void_p(y.data_ptr()), n),
+                    "gm_sac_learner_grad_q")
+        torch.cuda.synchronize(y.device)     # the env's stream, before torch reuses the tensors
+
+    def grad_pi(self, batch: dict, alpha: float | None = None, seed: int = 0, draw: int = 0, debug: bool = False):
+        """loss_pi.backward() for a sampled batch (state is read) with the critics as they stand,
+        row i drawing with (seed, i, draw): leaves the raw gradient of [pi] and loss_pi on the
+        device.  With debug, returns a dict of device tensors z, u, a [n, n_actions] and logp, q1,
+        q2 [n]: the draws, the pre-squash sample, the action, its log-probability and both critics."""
+        import torch
+        st = batch["state"]
+        n, na = int(st.shape[0]), self.env.n_actions
+        alpha = self.options["alpha"] if alpha is None else alpha
+        f = dict(dtype=torch.float32, device=st.device)
+        dbg = {}
+        if debug:
+            dbg = {k: torch.empty((n, na), **f) for k in ("z", "u", "a")}
+            dbg.update({k: torch.empty((n,), **f) for k in ("logp", "q1", "q2")})
+        ptr = [C.c_void_p(dbg[k].data_ptr()) if debug else None for k in ("z", "u", "a", "logp", "q1", "q2")]
+        b = _batch_struct(batch)
+        torch.cuda.synchronize(st.device)    # torch-side writes to the batch, the allocations
+        self._check(self.lib.gm_sac_learner_grad_pi(self._l, C.byref(b), n, C.c_float(alpha), C.c_uint64(seed),
+                                                    C.c_uint64(draw), *ptr), "gm_sac_learner_grad_pi")
+        torch.cuda.synchronize(st.device)    # the env's stream, before torch reads the outputs
+        return dbg if debug else None
+
+    def step_q(self):
+        """q_optimiser.step() on the held gradient, in place on [q1 | q2] of `sac`."""
+        self._check(self.lib.gm_sac_learner_step_q(self._l), "gm_sac_learner_step_q")
+
+    def step_pi(self):
+        """pi_optimiser.step() on the held gradient, in place on [pi] of `sac`."""
+        self._check(self.lib.gm_sac_learner_step_pi(self._l), "gm_sac_learner_step_pi")
+
+    def read(self):
+        """(both gradients as one array in init_params' flat order, loss_q, loss_pi) as the last
+        grad_q() / grad_pi() / update left them."""
+        g = np.empty(self.sac.params.size, dtype=np.float32)
+        lq, lp = C.c_float(), C.c_float()
+        self._check(self.lib.gm_sac_learner_read(self._l, g.ctypes.data_as(C.POINTER(C.c_float)), C.byref(lq),
+                                                 C.byref(lp)), "gm_sac_learner_read")
+        return g, float(lq.value), float(lp.value)
+
+    def state(self) -> dict:
+        """Both optimisers' state in flat order, like their state_dict()s' tensors: step_q, step_pi,
+        exp_avg, exp_avg_sq, max_exp_avg_sq (one array each: the critics' part is q_optimiser's)."""
+        f32p = C.POINTER(C.c_float)
+        n = self.sac.params.size
+        steps = (C.c_int64 * 2)()
+        out = {k: np.empty(n, dtype=np.float32) for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")}
+        self._check(self.lib.gm_sac_learner_get_state(self._l, steps, *(out[k].ctypes.data_as(f32p) for k in out)),
+                    "gm_sac_learner_get_state")
+        return dict(step_q=int(steps[0]), step_pi=int(steps[1]), **out)
+
+    def load_state(self, state: dict):
+        f32p = C.POINTER(C.c_float)
+        n = self.sac.params.size
+        arrs = [np.ascontiguousarray(as_f32(state[k]), np.float32).ravel()
+                for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")]
+        if any(a.size != n for a in arrs):
+            raise ValueError(f"{n} entries per moment expected")
+        steps = (C.c_int64 * 2)(int(state["step_q"]), int(state["step_pi"]))
+        self._check(self.lib.gm_sac_learner_set_state(self._l, steps, *(a.ctypes.data_as(f32p) for a in arrs)),
+                    "gm_sac_learner_set_state")
+
+    def train(self, buf: ActionReplayBuffer, n_updates: int, batch_size: int | None = None, seed: int = 0,
+              noise_seed: int = 1, draw0: int = 0, tau: float | None = None):
+        """n_updates of optimise_model enqueued back to back: sample(draw0 + u) -> backup -> critic
+        gradient and step -> actor gradient and step -> polyak update.  The backup's noise is keyed
+        (noise_seed, 2 (draw0 + u)), the actor loss's (noise_seed, 2 (draw0 + u) + 1).  tau: the
+        polyak factor (default soft_target_tau; 0 leaves the target alone).  Returns (loss_q,
+        loss_pi) of every update as a device tensor [n_updates, 2]."""
+        import torch
+        if self.target is None:
+            raise ValueError("train() needs the target handle")
+        dev = buf.state.device
+        o = self.options
+        losses = torch.empty((int(n_updates), 2), dtype=torch.float32, device=dev)
+        r = buf.struct()
+        torch.cuda.synchronize(dev)     # torch-side writes to the memory (tests), the allocation
+        self._check(self.lib.gm_sac_learner_train(
+            self._l, self.target._p, C.byref(r), len(buf), int(o["batch_size"] if batch_size is None else batch_size),
+            C.c_uint64(seed), C.c_uint64(noise_seed), C.c_uint64(draw0), int(n_updates), C.c_float(o["gamma"]),
+            C.c_float(o["alpha"]), int(self.bootstrap_truncated), C.c_float(o["soft_target_tau"] if tau is None else tau),
+            C.c_void_p(losses.data_ptr())), "gm_sac_learner_train")
+        torch.cuda.synchronize(dev)     # the env's stream, before torch reads the losses
+        return losses
+
+    def close(self):
+        if self._l:
+            self.lib.gm_sac_learner_destroy(self._l)
+            self._l = C.c_void_p()
 
     def __del__(self):
         try:

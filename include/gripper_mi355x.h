@@ -1002,8 +1002,7 @@ int  gm_ppo_learner_update(gm_ppo_learner* l, const gm_ac_traj* traj, int n_step
 
 /* ---- SAC: squashed Gaussian actor, action replay memory, twin critics and the soft Q target ----
  * The collection side of Agent_SAC (rl/agents/ActorCritic.py) and everything of its
- * optimise_model that is forward-only.  The learner (the backward of loss_q and loss_pi, the two
- * optimisers, the polyak update) is not here.
+ * optimise_model that is forward-only; the learner follows below ("SAC learner").
  *   actor    h = mlp([n_obs, *hidden], act, act)(obs): the activation follows every hidden Linear;
  *            mu = mu_layer(h), log_std = clamp(log_std_layer(h), log_std_min, log_std_max);
  *            u = mu + exp(log_std) z (GM_SAC_SAMPLE) or u = mu (GM_SAC_MEAN);
@@ -1044,7 +1043,8 @@ typedef struct gm_sac_batch {
   uint8_t* end;         /* [batch] */
   int32_t* index;       /* [batch] the ring rows gathered */
 } gm_sac_batch;
-/* sizeof of 0 gm_sac_replay, 1 gm_sac_batch, 2 gm_sac_opt (-1 otherwise): for bindings */
+/* sizeof of 0 gm_sac_replay, 1 gm_sac_batch, 2 gm_sac_opt, 4 gm_sac_learn_opt (-1 otherwise, 3
+ * included): for bindings */
 int64_t gm_sac_struct_size(int which);
 typedef struct gm_sac gm_sac;
 /* The device layout of the parameters: [pi | q1 | q2], each net in gm_policy_pack's layout; pi is
@@ -1107,6 +1107,76 @@ int  gm_sac_q(gm_sac* p, const float* state, const float* action, int n, float* 
 int  gm_sac_target(gm_sac* target, gm_sac* online, const gm_sac_batch* batch, int n, float gamma, float alpha,
                    int bootstrap_truncated, uint64_t seed, uint64_t draw, float* y, float* a2, float* u2,
                    float* logp2, float* qmin);
+
+/* ---- SAC learner: critic and actor backward, two optimisers and the polyak update ----
+ * Agent_SAC.optimise_model (rl/agents/ActorCritic.py:452-500) on the packed device weights
+ * [pi | q1 | q2] that gm_sac_rollout reads; no weight crosses the bus.  In the reference's order:
+ *   y        = gm_sac_target's backup
+ *   loss_q   = mean((q1(o, a) - y)^2) + mean((q2(o, a) - y)^2); q_optimiser steps [q1 | q2]
+ *   loss_pi  = mean(alpha logp_pi - min(q1, q2)(o, pi(o))) with the critics as that step left them,
+ *              frozen (none of their weight gradients is formed), and fresh noise; pi_optimiser
+ *              steps [pi].  A tie of the min goes to q1.
+ *   polyak   theta_targ <- (1 - tau) theta_targ + tau theta over all three nets.
+ * Optimisers as Agent_SAC.init builds them: "adam" is torch.optim.Adam(lr, betas); "adamW" is
+ * torch.optim.AdamW(lr, betas, amsgrad=True) with torch's weight_decay 0.01.  No gradient clamp.
+ * The reference hands pi_optimiser all of mlp_ac.parameters() under AdamW, but the critics' .grad
+ * is None when it steps (zero_grad sets None under torch >= 2.0), so it skips them, decay
+ * included: here pi_optimiser owns [pi] alone.  RMSprop is not on the device. */
+typedef struct gm_sac_learn_opt {   /* doubles, as torch keeps its hyperparameters */
+  int32_t optimiser;                /* GM_OPT_ADAM (default) / GM_OPT_ADAMW */
+  int32_t amsgrad;
+  double  lr, beta1, beta2, eps, weight_decay;
+} gm_sac_learn_opt;
+/* Agent_SAC.Parameters' defaults: Adam, lr 1e-4, betas (0.9, 0.999), eps 1e-8, no decay, no amsgrad */
+void gm_sac_learn_opt_default(gm_sac_learn_opt* out);
+/* A learner for `online`, on its context: owns the per-tile partial gradients, both summed
+ * gradients, exp_avg / exp_avg_sq / max_exp_avg_sq of both optimisers (zero), their step counts (0)
+ * and the scratch, sized for batches of up to GM_LEARNER_MAX_BATCH rows.  Destroy it before `online`. */
+typedef struct gm_sac_learner gm_sac_learner;
+int  gm_sac_learner_create(gm_sac* online, const gm_sac_learn_opt* opt, gm_sac_learner** out);
+void gm_sac_learner_destroy(gm_sac_learner* l);
+/* loss_q.backward() for the first n rows of a batch (state and action are read) and the backup y
+ * (device [n]): leaves the raw gradient of [q1 | q2] and loss_q on the device.
+ * n > GM_LEARNER_MAX_BATCH is GM_E_ARG. */
+int  gm_sac_learner_grad_q(gm_sac_learner* l, const gm_sac_batch* batch, const float* y, int n);
+/* loss_pi.backward() for the first n rows of a batch (state is read): row i draws with (seed, i,
+ * draw), gm_sac_target's keys.  Leaves the raw gradient of [pi] and loss_pi on the device; the
+ * critics' held gradient is untouched.  z, u, a: [n][n_actions], logp, q1, q2: [n]: optional
+ * device outputs (the draws, the pre-squash sample, the action, its log-probability and both
+ * critics on it), any may be NULL. */
+int  gm_sac_learner_grad_pi(gm_sac_learner* l, const gm_sac_batch* batch, int n, float alpha, uint64_t seed,
+                            uint64_t draw, float* z, float* u, float* a, float* logp, float* q1, float* q2);
+/* q_optimiser.step() / pi_optimiser.step() on the held gradient, in place on the online handle's
+ * device weights: [q1 | q2] alone / [pi] alone.  That optimiser's step count goes up by one. */
+int  gm_sac_learner_step_q(gm_sac_learner* l);
+int  gm_sac_learner_step_pi(gm_sac_learner* l);
+/* target <- tau online + (1 - tau) target over the whole blob (ActorCritic.py:494-500); the two
+ * handles need the same sizes and context.  The sum is formed in double and rounded once; tau = 1
+ * copies online bit for bit. */
+int  gm_sac_soft_update(gm_sac* target, gm_sac* online, float tau);
+/* Both held gradients in gm_sac_create's flat order (one array: [pi | q1 | q2]), loss_q and
+ * loss_pi (host pointers; any may be NULL). */
+int  gm_sac_learner_read(gm_sac_learner* l, float* grad_flat, float* loss_q, float* loss_pi);
+/* Both optimisers' state_dict() tensors in flat order (one array each: the [q1 | q2] part is
+ * q_optimiser's, the [pi] part pi_optimiser's); steps: [2] = q_optimiser's, pi_optimiser's.  Host
+ * pointers; any may be NULL. */
+int  gm_sac_learner_get_state(gm_sac_learner* l, int64_t* steps, float* exp_avg, float* exp_avg_sq,
+                              float* max_exp_avg_sq);
+int  gm_sac_learner_set_state(gm_sac_learner* l, const int64_t* steps, const float* exp_avg, const float* exp_avg_sq,
+                              const float* max_exp_avg_sq);
+/* n_updates of optimise_model enqueued with no host synchronisation between them: for u = 0 ..
+ * n_updates - 1, with d = draw0 + u,
+ *   gm_sac_replay_sample(size, batch, seed, d) into the learner's own batch arrays
+ *   -> gm_sac_target(target, online, gamma, alpha, bootstrap_truncated, noise_seed, 2 d)
+ *   -> gm_sac_learner_grad_q -> gm_sac_learner_step_q
+ *   -> gm_sac_learner_grad_pi(alpha, noise_seed, 2 d + 1) -> gm_sac_learner_step_pi
+ *   -> gm_sac_soft_update(target, online, tau)
+ * every result equal to the calls' bit for bit (each range's polyak update rides in that range's
+ * step launch, which is elementwise the same).  tau <= 0 skips the polyak update.  losses: device
+ * [n_updates][2] (loss_q, loss_pi of every update) or NULL. */
+int  gm_sac_learner_train(gm_sac_learner* l, gm_sac* target, const gm_sac_replay* replay, int64_t size, int batch,
+                          uint64_t seed, uint64_t noise_seed, uint64_t draw0, int n_updates, float gamma, float alpha,
+                          int bootstrap_truncated, float tau, float* losses);
 
 #ifdef __cplusplus
 }
