@@ -1,7 +1,7 @@
 // gm_ac.hip -- the batched PPO actor-critic kernels (gm_ac_act / gm_ac_record / gm_ac_finish)
 // and the GAE-lambda scan.  The forward is gm_policy_net.h's gp_forward_tile with each net's
-// activation code; sampling is gm_ac_net.h's ga_sample (both shared with gm_rollout's per-env
-// driver, gm_rollout.h ac_rollout_driver).
+// activation code; sampling is gm_ac_net.h's ga_sample / ga_sample_cat (both shared with
+// gm_rollout's per-env driver, gm_rollout.h ac_rollout_driver).
 #pragma once
 #include "gm_ac_net.h"
 
@@ -24,7 +24,15 @@ __global__ __launch_bounds__(64) void gm_ac_kernel(int what, const float* __rest
     const int na = A.net.actor.width[A.net.actor.n_layers];
     int cur = gp_forward_tile(obs, A.t_obs + (size_t)k * n_envs * n_obs, e0, n_envs, A.params, A.net.actor,
                               A.net.act_actor, act, lane);
-    if (mine) {
+    if (mine && A.net.categorical) {   // logits: the index as a float is the row's one action, the logits go to mu
+      const float* x = act[cur][lane];
+      A.t_logp[row] = ga_sample_cat(x, na, A.sample, A.seed, A.decision0 + (uint64_t)k,
+                                    (uint64_t)(env_offset + (long long)env), asamp[lane]);
+      A.t_act[row] = asamp[lane][0];
+      if (A.t_idx) A.t_idx[env] = (int)asamp[lane][0];
+      if (A.t_mu)
+        for (int i = 0; i < na; i++) A.t_mu[row * na + i] = x[i];
+    } else if (mine) {
       const float* mu = act[cur][lane];
       A.t_logp[row] = ga_sample(mu, A.params + A.net.log_std_off, na, A.sample, A.noise, A.seed,
                                 A.decision0 + (uint64_t)k, (uint64_t)(env_offset + (long long)env), asamp[lane]);

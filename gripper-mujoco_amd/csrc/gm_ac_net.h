@@ -27,6 +27,14 @@
 //   z  = sqrt(-2 log(u1)) cos(2 pi u2)                                (Box-Muller)
 //   u3 = (c_3 >> 40) / 2^24,  noise draw = noise (2 u3 - 1)           in [-noise, noise)
 // gmx/ppo.py normal_draws / noise_draws mirror this in float64.
+//
+// The categorical actor (MLPCategoricalActor, rl/agents/PolicyGradient.py:429-447, built by
+// MLPActorCriticPG(continous_actions=False)): the same MLP with its outputs read as logits,
+//   pi = Categorical(logits = logits_net(obs)),  a ~ pi,  logp = pi.log_prob(a)
+// and no log_std: the blob is [actor net | critic net] (GaNet::categorical, log_std_off then
+// the blob's end).  ga_sample_cat has the arithmetic; its one uniform per env is
+//   u = (gp_mix(h + 1) >> 40) / 2^24   in [0, 1)          (gmx/ppo.py categorical_uniforms)
+// and the action is the inverse CDF of the unnormalised e_j = exp(x_j - max x) at u * sum e.
 #pragma once
 #include "gm_policy_net.h"
 
@@ -38,6 +46,7 @@ struct GaNet {
   int act_actor, act_critic;    // hidden activation codes (GP_ACT_*)
   long long critic_off;         // float offset of the critic's packed net in the blob
   long long log_std_off;        // and of log_std
+  int categorical;              // the actor's outputs are logits; no log_std (log_std_off: the blob's end)
 };
 
 // one rollout launch's (or per-step call's) arguments; the trajectory pointers are indexed
@@ -47,7 +56,8 @@ struct GaArgs {
   const float* params;
   float* t_obs; float* t_act; float* t_logp; float* t_val; float* t_rew; uint8_t* t_end; float* t_boot;
   float* t_last_val; float* t_mu;
-  int sample;                   // 0: a = mu
+  int32_t* t_idx;               // categorical gm_ac_act: the chosen index per env for the discrete-action path, or NULL
+  int sample;                   // 0: a = mu (categorical: the argmax)
   float noise;
   uint64_t seed, decision0;     // env-step k of the launch draws with decision0 + k
 };
@@ -81,6 +91,44 @@ __device__ __noinline__ float ga_sample(const float* mu, const float* __restrict
     a[i] = ai;
   }
   return logp;
+}
+
+// The categorical actor's draw and log-probability for ONE env on ONE lane (as ga_sample: the
+// batched kernel and the rollout driver call this one function).  x: n logits.  In f32, in this order:
+//   m = max_j x_j;  e_j = expf(x_j - m);  s = sum_j e_j in index order;  lse = m + logf(s)
+//   logp_j = x_j - lse     (never logf(p_j): a p_j that underflows to 0 keeps a finite logp_j)
+//   t = u s;  a = the first j whose running sum of e exceeds t, else the last j with e_j > 0
+// (no division; the running sum is s's own, so it ends at s > t unless u s rounds up to s).
+// sample == 0: the argmax, the lowest index on a tie.  Returns logp_a; *idx = the index a in
+// [0, n) as a float, as the trajectory stores it (a caller's row, like ga_sample's a: a pointer to
+// a local would cost the batched kernel a stack slot).
+__device__ __noinline__ float ga_sample_cat(const float* x, int n, int sample, uint64_t seed, uint64_t decision,
+                                            uint64_t gid, float* idx) {
+  float m = x[0];
+  int a = 0;
+  for (int j = 1; j < n; j++)
+    if (x[j] > m) { m = x[j]; a = j; }
+  float s = 0.0f;
+  for (int j = 0; j < n; j++) s += expf(x[j] - m);
+  const float lse = m + logf(s);
+  if (sample) {
+    const uint64_t h = gp_mix(seed ^ gp_mix(gid * 0x100000001B3ull + decision));
+    const uint64_t c = gp_mix(h + 1ull);
+    const float u = (float)((double)(c >> 40) * (1.0 / 16777216.0));
+    const float t = u * s;
+    float run = 0.0f;
+    int last = 0;
+    a = -1;
+    for (int j = 0; j < n && a < 0; j++) {
+      const float e = expf(x[j] - m);
+      if (e > 0.0f) last = j;
+      run += e;
+      if (run > t) a = j;
+    }
+    if (a < 0) a = last;
+  }
+  *idx = (float)a;
+  return x[a] - lse;
 }
 
 // The critic alone for one env (gm_ac_record's bootstrap value, gm_ac_finish's last value).

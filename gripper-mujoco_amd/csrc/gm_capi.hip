@@ -1834,8 +1834,9 @@ struct gm_ac {
 
 static_assert(GA_MAX_ACT >= GM_ACTION_CODE_COUNT, "the sampler's rows hold every action");
 
-static int64_t ac_layout(const int32_t* asz, int na, const int32_t* csz, int nc, GaNet* net, int64_t* n_raw) {
-  return gq_layout(asz, na, csz, nc, net, n_raw);
+static int64_t ac_layout(const int32_t* asz, int na, const int32_t* csz, int nc, GaNet* net, int64_t* n_raw,
+                         int categorical = 0) {
+  return gq_layout(asz, na, csz, nc, net, n_raw, categorical);
 }
 
 // the device-side view of a caller's trajectory buffer
@@ -1845,6 +1846,7 @@ static void ac_fill(GaArgs& A, const gm_ac* p, const gm_ac_traj* t, int sample, 
   A.params = p->d_params;
   A.t_obs = t->obs; A.t_act = t->act; A.t_logp = t->logp; A.t_val = t->val; A.t_rew = t->rew; A.t_end = t->end;
   A.t_boot = t->boot; A.t_last_val = t->last_val; A.t_mu = t->mu;
+  A.t_idx = nullptr;
   A.sample = sample;
   A.noise = noise;
   A.seed = seed;
@@ -1860,9 +1862,12 @@ static int ac_step(gm_ac* p, const gm_ac_traj* t, int k, int what, int max_ep, c
   if (!p || !p->ctx) return GM_E_ARG;
   gm_ctx* c = p->ctx;
   if (!ac_traj_ok(t) || k < 0 || k >= t->capacity || !(noise >= 0.0f)) return fail(c, GM_E_ARG, bad);
+  if (p->net.categorical && noise != 0.0f)
+    return fail(c, GM_E_ARG, "gm_ac_act: a categorical actor takes no exploration noise (noise must be 0)");
   HIPCHK(c, hipSetDevice(c->device));
   GaArgs A{};
   ac_fill(A, p, t, sample, noise, seed, decision0);
+  if (p->net.categorical && what == 0) A.t_idx = c->d_dact;
   const int blocks = (c->n_envs + GP_TILE - 1) / GP_TILE;
   hipLaunchKernelGGL(gm_ac_kernel, dim3(blocks), dim3(64), 0, c->stream, what, c->d_obs, c->d_state, c->d_rew,
                      c->d_done, c->n_envs, (long long)c->env_offset, A, k, max_ep);
@@ -1870,13 +1875,12 @@ static int ac_step(gm_ac* p, const gm_ac_traj* t, int k, int what, int max_ep, c
   return GM_OK;
 }
 
-extern "C" {
-
-int64_t gm_ac_pack(const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes, int n_critic,
-                   const float* params, float* out, int64_t* off2) {
+// gm_ac_pack (categorical 0) and gm_ac_pack_categorical (1)
+static int64_t ac_pack(int categorical, const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes,
+                       int n_critic, const float* params, float* out, int64_t* off2) {
   GaNet N;
   if (!actor_sizes || !critic_sizes || n_actor < 2 || n_critic < 2) return -1;
-  const int64_t total = ac_layout(actor_sizes, n_actor, critic_sizes, n_critic, &N, nullptr);
+  const int64_t total = ac_layout(actor_sizes, n_actor, critic_sizes, n_critic, &N, nullptr, categorical);
   if (total < 0) return total;
   if (off2) { off2[0] = N.critic_off; off2[1] = N.log_std_off; }
   if (!out) return total;
@@ -1886,24 +1890,28 @@ int64_t gm_ac_pack(const int32_t* actor_sizes, int n_actor, const int32_t* criti
   for (int l = 0; l + 1 < n_actor; l++) src += (size_t)actor_sizes[l + 1] * actor_sizes[l] + actor_sizes[l + 1];
   gm_policy_pack(critic_sizes, n_critic, src, out + N.critic_off);
   for (int l = 0; l + 1 < n_critic; l++) src += (size_t)critic_sizes[l + 1] * critic_sizes[l] + critic_sizes[l + 1];
-  std::memcpy(out + N.log_std_off, src, sizeof(float) * (size_t)actor_sizes[n_actor - 1]);
+  if (!categorical) std::memcpy(out + N.log_std_off, src, sizeof(float) * (size_t)actor_sizes[n_actor - 1]);
   return total;
 }
 
-int gm_ac_create(gm_ctx* c, const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes, int n_critic,
-                 const float* params, gm_ac** out) {
+// gm_ac_create (categorical 0) and gm_ac_create_categorical (1); the messages name the caller's entry point
+static int ac_create(int categorical, gm_ctx* c, const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes,
+                     int n_critic, const float* params, gm_ac** out) {
+  const std::string who = categorical ? "gm_ac_create_categorical: " : "gm_ac_create: ";
   if (!c || !actor_sizes || !critic_sizes || !params || !out || n_actor < 2 || n_critic < 2) return GM_E_ARG;
   GaNet N;
   int64_t n_raw = 0;
-  const int64_t total = ac_layout(actor_sizes, n_actor, critic_sizes, n_critic, &N, &n_raw);
-  if (total < 0) return fail(c, GM_E_ARG, "gm_ac_create: <= 8 layers of width 1..256 expected");
-  if (!c->cfg.s.continous_actions)
-    return fail(c, GM_E_ARG, "gm_ac_create: the Gaussian actor needs continuous actions (continous_actions != 0)");
+  const int64_t total = ac_layout(actor_sizes, n_actor, critic_sizes, n_critic, &N, &n_raw, categorical);
+  if (total < 0) return fail(c, GM_E_ARG, who + "<= 8 layers of width 1..256 expected");
+  if (!categorical && !c->cfg.s.continous_actions)
+    return fail(c, GM_E_ARG, who + "the Gaussian actor needs continuous actions (continous_actions != 0)");
+  if (categorical && c->cfg.s.continous_actions)
+    return fail(c, GM_E_ARG, who + "the categorical actor needs discrete actions (continous_actions == 0)");
   if (N.actor.width[0] != c->cfg.n_obs || N.actor.width[N.actor.n_layers] != c->cfg.n_actions)
-    return fail(c, GM_E_ARG, "gm_ac_create: the actor must map n_obs (" + std::to_string(c->cfg.n_obs) +
+    return fail(c, GM_E_ARG, who + "the actor must map n_obs (" + std::to_string(c->cfg.n_obs) +
                                  ") to n_actions (" + std::to_string(c->cfg.n_actions) + ")");
   if (N.critic.width[0] != c->cfg.n_obs || N.critic.width[N.critic.n_layers] != 1)
-    return fail(c, GM_E_ARG, "gm_ac_create: the critic must map n_obs (" + std::to_string(c->cfg.n_obs) + ") to 1");
+    return fail(c, GM_E_ARG, who + "the critic must map n_obs (" + std::to_string(c->cfg.n_obs) + ") to 1");
   HIPCHK(c, hipSetDevice(c->device));
   gm_ac* p = new gm_ac;
   p->ctx = c;
@@ -1916,12 +1924,34 @@ int gm_ac_create(gm_ctx* c, const int32_t* actor_sizes, int n_actor, const int32
   if (e == hipSuccess) e = p->d_args.alloc(1);
   if (e != hipSuccess) {
     gm_ac_destroy(p);
-    return fail(c, GM_E_HIP, std::string("gm_ac_create: ") + hipGetErrorString(e));
+    return fail(c, GM_E_HIP, who + hipGetErrorString(e));
   }
   const int rc = gm_ac_set_params(p, params);
   if (rc != GM_OK) { gm_ac_destroy(p); return rc; }
   *out = p;
   return GM_OK;
+}
+
+extern "C" {
+
+int64_t gm_ac_pack(const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes, int n_critic,
+                   const float* params, float* out, int64_t* off2) {
+  return ac_pack(0, actor_sizes, n_actor, critic_sizes, n_critic, params, out, off2);
+}
+
+int64_t gm_ac_pack_categorical(const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes, int n_critic,
+                               const float* params, float* out, int64_t* off2) {
+  return ac_pack(1, actor_sizes, n_actor, critic_sizes, n_critic, params, out, off2);
+}
+
+int gm_ac_create(gm_ctx* c, const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes, int n_critic,
+                 const float* params, gm_ac** out) {
+  return ac_create(0, c, actor_sizes, n_actor, critic_sizes, n_critic, params, out);
+}
+
+int gm_ac_create_categorical(gm_ctx* c, const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes,
+                             int n_critic, const float* params, gm_ac** out) {
+  return ac_create(1, c, actor_sizes, n_actor, critic_sizes, n_critic, params, out);
 }
 
 void gm_ac_destroy(gm_ac* p) {
@@ -1938,7 +1968,8 @@ int gm_ac_set_params(gm_ac* p, const float* params) {
   gm_ctx* c = p->ctx;
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<float> packed((size_t)p->total);
-  gm_ac_pack(p->asz.data(), (int)p->asz.size(), p->csz.data(), (int)p->csz.size(), params, packed.data(), nullptr);
+  ac_pack(p->net.categorical, p->asz.data(), (int)p->asz.size(), p->csz.data(), (int)p->csz.size(), params,
+          packed.data(), nullptr);
   return stage_upload(c, p->d_params, packed.data(), sizeof(float) * (size_t)p->total);
 }
 
@@ -1949,6 +1980,8 @@ int gm_ac_act(gm_ac* p, const gm_ac_traj* traj, int k, int sample, float noise, 
               sample, noise, seed, decision - (uint64_t)k);
   if (rc != GM_OK) return rc;
   gm_ctx* c = p->ctx;
+  // (categorical: the kernel left the chosen indices in d_dact; gm_policy_act's path, lift substeps included)
+  if (p->net.categorical) return gm_set_discrete_action(c, c->d_dact, 1);
   return gm_set_action(c, traj->act + (size_t)k * c->n_envs * c->cfg.n_actions, 1);
 }
 
@@ -1966,6 +1999,8 @@ int gm_ac_rollout(gm_ac* p, const gm_ac_traj* traj, int n_steps, int sample, flo
   gm_ctx* c = p->ctx;
   if (!ac_traj_ok(traj) || n_steps < 1 || n_steps > traj->capacity || !(noise >= 0.0f))
     return fail(c, GM_E_ARG, "gm_ac_rollout: incomplete trajectory buffer, n_steps outside its capacity or negative noise");
+  if (p->net.categorical && noise != 0.0f)
+    return fail(c, GM_E_ARG, "gm_ac_rollout: a categorical actor takes no exploration noise (noise must be 0)");
   HIPCHK(c, hipSetDevice(c->device));
   if (chunk_queue_on(c)) {
     GaArgs A{};
@@ -2036,6 +2071,7 @@ static hipError_t ppo_launch_grad(gm_ppo_learner* l, bool policy, const gm_ppo_b
   const gm_ac* p = l->ac;
   const GaNet& N = p->net;
   const int n_act = N.actor.width[N.actor.n_layers];
+  const int n_ls = N.categorical ? 0 : n_act;     // log_std entries, behind the critic
   GqGradArgs a{};
   a.obs = b.obs; a.act = b.act; a.logp_old = b.logp; a.adv = b.adv; a.ret = b.ret;
   a.n = b.n;
@@ -2057,8 +2093,12 @@ static hipError_t ppo_launch_grad(gm_ppo_learner* l, bool policy, const gm_ppo_b
   a.total = (long long)p->total;
   a.wg_info = l->d_wg;
   a.stop = stop;
+  a.use_ent = l->opt.use_entropy_regularisation != 0;
+  a.c_ent = (float)l->opt.entropy_coefficient;
   const size_t lds = sizeof(float) * (size_t)(a.plan.total <= GL_ARENA ? a.plan.total + (a.lds_part ? a.net_total : 0) : 0);
-  if (policy)
+  if (policy && N.categorical)
+    hipLaunchKernelGGL(gm_ppo_grad_pi_cat_kernel, dim3(l->groups), dim3(64), lds, c->stream, a);
+  else if (policy)
     hipLaunchKernelGGL(gm_ppo_grad_pi_kernel, dim3(l->groups), dim3(64), lds, c->stream, a);
   else
     hipLaunchKernelGGL(gm_ppo_grad_vf_kernel, dim3(l->groups), dim3(64), lds, c->stream, a);
@@ -2070,7 +2110,7 @@ static hipError_t ppo_launch_grad(gm_ppo_learner* l, bool policy, const gm_ppo_b
   r.partials = l->d_partials;
   r.total = a.total;
   r.n_parts = (int)std::min<long long>(l->groups, tiles);
-  r.count = policy ? ta + n_act : tc;
+  r.count = policy ? ta + n_ls : tc;
   r.first = policy ? 0 : ta;
   r.gap_at = policy ? ta : r.count;
   r.gap_len = policy ? tc : 0;
@@ -2090,6 +2130,7 @@ static hipError_t ppo_launch_grad(gm_ppo_learner* l, bool policy, const gm_ppo_b
   r.last_out = last;
   r.stop = stop;
   r.kl_stop = l->opt.max_kl_ratio * l->opt.target_kl;
+  r.categorical = N.categorical;
   const int threads = 256;
   hipLaunchKernelGGL(gm_ppo_reduce_kernel, dim3((unsigned)((r.count + threads - 1) / threads)), dim3(threads), 0,
                      c->stream, r);
@@ -2103,7 +2144,7 @@ static hipError_t ppo_launch_step(gm_ppo_learner* l, bool policy, int64_t t, con
   const long long first = policy ? 0 : ta;
   GlStepArgs a{};
   a.do_step = 1;
-  a.total = policy ? ta + N.actor.width[N.actor.n_layers] : tc;
+  a.total = policy ? ta + (N.categorical ? 0 : N.actor.width[N.actor.n_layers]) : tc;
   a.gap_at = policy ? ta : 0;
   a.gap_len = policy ? tc : 0;
   a.grad = l->d_grad + first;

@@ -8,7 +8,9 @@
 //   [actor net | critic net | log_std[n_actions]]
 // the steps update gm_ac's d_params in place and nothing is repacked.  Padding entries stay 0 by
 // gm_learn.h's argument: a padding weight's activation column or delta column is 0, so its
-// gradient is 0, and 0 stays 0 under Adam and AdamW (log_std has no padding).
+// gradient is 0, and 0 stays 0 under Adam and AdamW (log_std has no padding).  A categorical
+// actor's blob (GaNet::categorical) is [actor net | critic net]: log_std has no entries, in the
+// blob, the flat order, either optimiser's range or the state calls.
 //
 // Tiles and workgroups.  A batch of n rows is ceil(n / 16) tiles of 16 rows.  A learner has a
 // fixed number G of workgroups; workgroup g takes tiles g, g + G, g + 2 G, ... in that order and
@@ -25,12 +27,16 @@
 #define GQ_DEFAULT_GROUPS 512   // profiles/ppo_learn.json: the G sweep at n = 40,960, (64, 64) nets
 #define GQ_MAX_GROUPS 4096
 #define GQ_LDS_FLOATS 16320     // floats of dynamic LDS a gradient workgroup may take (64 KB less the static rows)
-#define GQ_INFO 4               // floats of wg_info per workgroup: loss sum, kl sum, clipped rows, unused
+#define GQ_INFO 4               // floats of wg_info per workgroup: loss sum, kl sum, clipped rows, entropy sum (categorical)
+// gq_grad's instantiations: the critic, the Gaussian policy, the categorical policy
+#define GQ_VF 0
+#define GQ_PI 1
+#define GQ_CAT 2
 
 // one launch of gm_ppo_grad_pi_kernel / gm_ppo_grad_vf_kernel
 struct GqGradArgs {
   const float* obs;             // [n][n_obs]
-  const float* act;             // [n][n_act]     (actor)
+  const float* act;             // [n][n_act]     (actor; categorical: [n][1], the index as a float)
   const float* logp_old;        // [n]            (actor)
   const float* adv;             // [n]            (actor)
   const float* ret;             // [n]            (critic)
@@ -52,6 +58,8 @@ struct GqGradArgs {
   long long total;              // blob floats
   float* wg_info;               // [n_groups][GQ_INFO]
   const int* stop;              // NULL, or the KL stop's latch: nonzero makes the launch a no-op
+  int use_ent;                  // (categorical) the entropy term's gradient goes into the output deltas
+  float c_ent;                  // entropy_coefficient
 };
 
 // gm_ppo_learner_read's / gm_ppo_info's scalar order
@@ -84,6 +92,7 @@ struct GqReduceArgs {
   float* last_out;              // [GQ_SCALARS] or NULL: and its last one
   int* stop;                    // NULL: no stop; else [0] the latch, [1] policy iterations that stepped
   double kl_stop;               // max_kl_ratio * target_kl
+  int categorical;              // ent = wg_info's fourth sum / n, and no log_std term
 };
 
 // the rows of the plan stay in LDS and the net's packed partial fits behind them
@@ -92,7 +101,8 @@ inline bool gq_lds_part(const GlPlan& L, long long net_total) {
 }
 
 // ---- host: layout and the flat <-> packed walk
-inline int64_t gq_layout(const int32_t* asz, int na, const int32_t* csz, int nc, GaNet* net, int64_t* n_raw) {
+inline int64_t gq_layout(const int32_t* asz, int na, const int32_t* csz, int nc, GaNet* net, int64_t* n_raw,
+                         int categorical = 0) {
   GaNet N{};
   const int64_t ta = gl_layout(asz, na, &N.actor);
   const int64_t tc = gl_layout(csz, nc, &N.critic);
@@ -100,16 +110,18 @@ inline int64_t gq_layout(const int32_t* asz, int na, const int32_t* csz, int nc,
   N.act_actor = N.act_critic = GP_ACT_TANH;
   N.critic_off = ta;
   N.log_std_off = ta + tc;
+  N.categorical = categorical != 0;
+  const int n_ls = categorical ? 0 : asz[na - 1];
   if (net) *net = N;
-  if (n_raw) *n_raw = gl_flat_count(N.actor) + gl_flat_count(N.critic) + asz[na - 1];
-  return ta + tc + asz[na - 1];
+  if (n_raw) *n_raw = gl_flat_count(N.actor) + gl_flat_count(N.critic) + n_ls;
+  return ta + tc + n_ls;
 }
 template <class F>
 inline void gq_for_each_param(const GaNet& N, F f) {   // f(flat index, packed index)
   const int64_t fa = gl_flat_count(N.actor), fc = gl_flat_count(N.critic);
   gl_for_each_param(N.actor, [&](int64_t i, int64_t k) { f(i, k); });
   gl_for_each_param(N.critic, [&](int64_t i, int64_t k) { f(fa + i, (int64_t)N.critic_off + k); });
-  const int n_act = N.actor.width[N.actor.n_layers];
+  const int n_act = N.categorical ? 0 : N.actor.width[N.actor.n_layers];
   for (int i = 0; i < n_act; i++) f(fa + fc + i, (int64_t)N.log_std_off + i);
 }
 // packed [total] -> flat [n_raw], and back (padding entries 0)

@@ -1,5 +1,6 @@
 // gm_ppo_learn.hip -- the PPO learner's kernels: the gradients of compute_loss_pi and
-// compute_loss_v over a batch (gm_ppo_grad_pi_kernel, gm_ppo_grad_vf_kernel: one wave per
+// compute_loss_v over a batch (gm_ppo_grad_pi_kernel, its categorical twin
+// gm_ppo_grad_pi_cat_kernel and gm_ppo_grad_vf_kernel: one wave per
 // workgroup, G workgroups, each over its own tiles of 16 rows), the kernel that sums the G
 // partial gradients in order, forms the losses and info scalars and latches the KL stop
 // (gm_ppo_reduce_kernel), and PPOBuffer.get's advantage normalisation
@@ -19,10 +20,19 @@
 //   dL/dmu_a = dL/dlogp (act_a - mu_a) / sigma_a^2           the deltas of the actor's outputs
 //   dL/dlog_std_a += dL/dlogp ((act_a - mu_a)^2 / sigma_a^2 - 1)   summed over the rows in row order
 // else the critic: loss_i = (v - ret)^2, delta = 2 (v - ret) / n.
-template <bool POLICY>
+// GQ_CAT, the categorical policy: the outputs x_j are logits and act[row][0] the taken index a
+// (clamped into the row).  In ga_sample_cat's order
+//   m = max_j x_j, e_j = expf(x_j - m), s = sum_j e_j, lse = m + logf(s), logp_j = x_j - lse
+//   logp = logp_a;  r, loss_i, dL/dlogp, kl and cf exactly as above
+//   p_j = e_j / s,  H = -sum_j p_j logp_j     (a class with e_j == 0 adds exactly 0)
+//   delta_j = dL/dlogp ([j == a] - p_j)  + (c_ent / n) p_j (logp_j + H) with entropy regularisation
+// (d(-c_ent mean H)/dx_j; the reduce kernel takes ent = mean H from the fourth row sum).
+template <int MODE>
 __device__ __forceinline__ void gq_grad(const GqGradArgs& a) {
+  constexpr bool POLICY = MODE == GQ_PI;
+  constexpr int N_INFO = MODE == GQ_CAT ? 4 : MODE == GQ_PI ? 3 : 1;
   extern __shared__ float arena[];               // the plan's rows when they fit GL_ARENA (then the partial, lds_part)
-  __shared__ float row_info[3][GP_TILE];         // per row: loss, logp_old - logp, clipped
+  __shared__ float row_info[MODE == GQ_CAT ? 4 : 3][GP_TILE];   // per row: loss, logp_old - logp, clipped, (GQ_CAT) entropy
   if (a.stop && *a.stop) return;                 // (uniform) the KL stop has latched
   const int lane = threadIdx.x;
   const GpNet& P = a.net;
@@ -40,7 +50,7 @@ __device__ __forceinline__ void gq_grad(const GqGradArgs& a) {
   const int n_out = P.width[nl];
   const int Sd = L.d_stride;
   const int wd = P.tiles[nl - 1] * 16;
-  float sums[3] = {0.0f, 0.0f, 0.0f};            // lane 0: this workgroup's loss, kl and clipped sums
+  float sums[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // lane 0: this workgroup's loss, kl, clipped and entropy sums
   bool add = false;
   for (size_t tile = blockIdx.x; tile < tiles; tile += (size_t)a.n_groups) {
     const size_t e0 = tile * GP_TILE;
@@ -52,9 +62,46 @@ __device__ __forceinline__ void gq_grad(const GqGradArgs& a) {
       float* drow = base + L.d_off[0] + lane * Sd;
       float* srow = base + L.d_off[1] + lane * Sd;    // (policy) the row's log_std gradient terms
       const float* out = base + L.a_off[nl] + lane * L.a_stride[nl];
-      float ls = 0.0f, kl = 0.0f, cf = 0.0f;
+      float ls = 0.0f, kl = 0.0f, cf = 0.0f, en = 0.0f;
       if (row < n) {
-        if (POLICY) {
+        if (MODE == GQ_CAT) {
+          float m = out[0];
+          for (int j = 1; j < n_out; j++)
+            if (out[j] > m) m = out[j];
+          float s = 0.0f;
+          for (int j = 0; j < n_out; j++) {
+            const float e = expf(out[j] - m);
+            srow[j] = e;                         // (the row the Gaussian keeps its log_std terms in)
+            s += e;
+          }
+          const float lse = m + logf(s);
+          int ai = (int)a.act[row];
+          ai = ai < 0 ? 0 : (ai >= n_out ? n_out - 1 : ai);
+          const float logp = out[ai] - lse;
+          const float lold = a.logp_old[row], A = a.adv[row];
+          const float r = expf(logp - lold);
+          float dl;
+          if (a.use_kl) {
+            ls = -(r * A);
+            dl = -(A * r + a.beta) / (float)n;
+          } else {
+            ls = -fminf(r * A, fminf(fmaxf(r, a.clip_lo), a.clip_hi) * A);
+            const bool flat = (r > a.clip_hi && A > 0.0f) || (r < a.clip_lo && A < 0.0f);
+            dl = flat ? 0.0f : -(A * r) / (float)n;
+          }
+          kl = lold - logp;
+          cf = (r > a.clip_hi || r < a.clip_lo) ? 1.0f : 0.0f;
+          float hs = 0.0f;
+          for (int j = 0; j < n_out; j++) hs += (srow[j] / s) * (out[j] - lse);
+          en = -hs;
+          const float ce = a.c_ent / (float)n;
+          for (int j = 0; j < n_out; j++) {
+            const float p = srow[j] / s;
+            float d = dl * ((j == ai ? 1.0f : 0.0f) - p);
+            if (a.use_ent) d = d + ce * (p * ((out[j] - lse) + en));
+            drow[j] = d;
+          }
+        } else if (POLICY) {
           const float* ac = a.act + row * (size_t)n_out;
           float logp = 0.0f;
           for (int i = 0; i < n_out; i++) {
@@ -97,10 +144,11 @@ __device__ __forceinline__ void gq_grad(const GqGradArgs& a) {
       row_info[0][lane] = ls;
       row_info[1][lane] = kl;
       row_info[2][lane] = cf;
+      if (MODE == GQ_CAT) row_info[3][lane] = en;
     }
     __syncthreads();
     if (lane == 0)
-      for (int q = 0; q < (POLICY ? 3 : 1); q++) {
+      for (int q = 0; q < N_INFO; q++) {
         float s = 0.0f;
         for (int r = 0; r < GP_TILE; r++) s += row_info[q][r];
         sums[q] += s;
@@ -125,11 +173,13 @@ __device__ __forceinline__ void gq_grad(const GqGradArgs& a) {
     w[0] = sums[0];
     w[1] = sums[1];
     w[2] = sums[2];
+    if (MODE == GQ_CAT) w[3] = sums[3];
   }
 }
 
-__global__ __launch_bounds__(64) void gm_ppo_grad_pi_kernel(GqGradArgs a) { gq_grad<true>(a); }
-__global__ __launch_bounds__(64) void gm_ppo_grad_vf_kernel(GqGradArgs a) { gq_grad<false>(a); }
+__global__ __launch_bounds__(64) void gm_ppo_grad_pi_kernel(GqGradArgs a) { gq_grad<GQ_PI>(a); }
+__global__ __launch_bounds__(64) void gm_ppo_grad_pi_cat_kernel(GqGradArgs a) { gq_grad<GQ_CAT>(a); }
+__global__ __launch_bounds__(64) void gm_ppo_grad_vf_kernel(GqGradArgs a) { gq_grad<GQ_VF>(a); }
 
 // grad = the sum of the workgroups' partials in workgroup order, for one optimiser's elements;
 // with entropy regularisation -c_ent / n_act more on every log_std element (the entropy of Normal
@@ -144,7 +194,7 @@ __global__ __launch_bounds__(256) void gm_ppo_reduce_kernel(GqReduceArgs a) {
   const long long e = a.first + i + (i >= a.gap_at ? a.gap_len : 0);
   float g = 0.0f;
   for (int p = 0; p < a.n_parts; p++) g += a.partials[(size_t)p * (size_t)a.total + (size_t)e];
-  if (a.policy && a.use_ent && e >= a.log_std_off) g = g - a.c_ent / (float)a.n_act;
+  if (a.policy && a.use_ent && !a.categorical && e >= a.log_std_off) g = g - a.c_ent / (float)a.n_act;
   a.grad[e] = g;
   if (i != 0) return;
   float s[3] = {0.0f, 0.0f, 0.0f};
@@ -160,8 +210,13 @@ __global__ __launch_bounds__(256) void gm_ppo_reduce_kernel(GqReduceArgs a) {
   }
   const float kl = s[1] / nf;
   float ent = 0.0f;
-  for (int j = 0; j < a.n_act; j++) ent += 1.41893853320467274178f + a.params[a.log_std_off + j];
-  ent = ent / (float)a.n_act;
+  if (a.categorical) {   // the mean of the rows' entropies, summed like the other three
+    for (int p = 0; p < a.n_parts; p++) ent += a.wg_info[(size_t)p * GQ_INFO + 3];
+    ent = ent / nf;
+  } else {
+    for (int j = 0; j < a.n_act; j++) ent += 1.41893853320467274178f + a.params[a.log_std_off + j];
+    ent = ent / (float)a.n_act;
+  }
   float loss = s[0] / nf;
   if (a.use_kl) loss = loss + a.beta * kl;
   if (a.use_ent) loss = loss - a.c_ent * ent;

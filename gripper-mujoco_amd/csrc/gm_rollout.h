@@ -107,7 +107,8 @@ __device__ __noinline__ void sac_rollout_driver(const GsArgs* __restrict__ Ap, c
 // wave, kept out of the substep loop's instruction stream (called between env-steps only).
 //   phase 0, before the env-step: gm_ac_act on this env alone -- observation, mu, the sampled
 //     action, logp and V(obs) into trajectory row k, then lane 0 applies the clipped actions in
-//     order (gm_action_kernel's loop);
+//     order (gm_action_kernel's loop); a categorical actor's row holds the logits, the
+//     chosen index as a float and its logp, and lane 0 applies the index as GM_DRV_DQN does;
 //   phase 1, after the epilogue and before the auto-reset: gm_ac_record -- reward, end code
 //     and, for a truncated env only, the critic on the post-step observation;
 //   phase 2, after the env's last env-step: gm_ac_finish -- the critic on the observation left
@@ -130,7 +131,14 @@ __device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restri
     const int na = A.net.actor.width[A.net.actor.n_layers];
     const int cur = gp_forward_one(obs, A.t_obs + row * n_obs, A.params, A.net.actor, A.net.act_actor, scratch, lane);
     float* a = scratch + 2 * GP_ROW;
-    if (lane == 0) {
+    const bool cat = A.net.categorical != 0;   // (uniform) logits -> index, applied as GM_DRV_DQN applies its own
+    if (lane == 0 && cat) {
+      const float* x = scratch + cur * GP_ROW;
+      A.t_logp[row] = ga_sample_cat(x, na, A.sample, A.seed, A.decision0 + (uint64_t)k, (uint64_t)gid, a);
+      A.t_act[row] = a[0];
+      if (A.t_mu)
+        for (int i = 0; i < na; i++) A.t_mu[row * na + i] = x[i];
+    } else if (lane == 0) {
       const float* mu = scratch + cur * GP_ROW;
       A.t_logp[row] = ga_sample(mu, A.params + A.net.log_std_off, na, A.sample, A.noise, A.seed,
                                 A.decision0 + (uint64_t)k, (uint64_t)gid, a);
@@ -145,10 +153,16 @@ __device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restri
     const float v = ga_value_one(obs, A, scratch, lane);
     if (lane == 0) {
       A.t_val[row] = v;
-      for (int i = 0; i < na; i++) {
+      // One call site for both actors: the categorical index, or every clipped action in order.
+      // a[0] holds the index as ga_sample_cat stored it: an integer below GA_MAX_ACT, exact in a
+      // float, so (int) gives it back.  It has to survive the critic forward above: ga_value_one
+      // uses scratch[0 .. 2 GP_ROW) only and must not touch a = scratch + 2 GP_ROW.
+      for (int i = 0; i < (cat ? 1 : na); i++) {
         float f = a[i];
-        if (f < -1.0f) f = -1.0f; else if (f > 1.0f) f = 1.0f;
-        set_action_one(s, m, C, i, f);
+        int which = i;
+        if (cat) { which = (int)f; f = 0.0f; }
+        else if (f < -1.0f) f = -1.0f; else if (f > 1.0f) f = 1.0f;
+        set_action_one(s, m, C, which, f);
       }
     }
   } else if (phase == 1) {

@@ -12,7 +12,7 @@ from ._lib import (load_library, Settings, ModelParams, Object, Spawn, SpawnPara
 from .settings import canonical_settings, disable_noise, MAX_EPISODE_STEPS
 from .env import BatchedGripperEnv, spawn_draws, spawn_int, random_fractions
 from .policy import DevicePolicy, DeviceLearner, ReplayBuffer, eps_threshold, dqn_opt, dqn_opt_default
-from .ppo import DeviceActorCritic, TrajectoryBuffer, DevicePPOLearner, ppo_opt, ppo_opt_default
+from .ppo import DeviceActorCritic, DeviceCategoricalActorCritic, TrajectoryBuffer, DevicePPOLearner, ppo_opt, ppo_opt_default
 from .sac import DeviceSAC, ActionReplayBuffer, DeviceSACLearner, SAC_DEFAULTS, sac_options, sac_opt
 from .scripted import GraspScript, in_use_actions
 
@@ -23,6 +23,6 @@ __all__ = ["load_library", "Settings", "ModelParams", "Object", "Spawn", "SpawnP
            "BatchedGripperEnv", "spawn_draws", "spawn_int", "random_fractions", "MAX_EPISODE_STEPS", "BINARY_EVENTS",
            "LINEAR_EVENTS", "ACTION_KINDS", "SENSORS", "LIB_PATH", "DevicePolicy", "ReplayBuffer", "eps_threshold",
            "DeviceLearner", "dqn_opt", "dqn_opt_default",
-           "DeviceActorCritic", "TrajectoryBuffer", "DevicePPOLearner", "ppo_opt", "ppo_opt_default",
+           "DeviceActorCritic", "DeviceCategoricalActorCritic", "TrajectoryBuffer", "DevicePPOLearner", "ppo_opt", "ppo_opt_default",
            "DeviceSAC", "ActionReplayBuffer", "DeviceSACLearner", "SAC_DEFAULTS", "sac_options", "sac_opt",
            "GraspScript", "in_use_actions", "env_state_dtype", "env_state_view"]

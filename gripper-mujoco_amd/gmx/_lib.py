@@ -379,6 +379,8 @@ def _declare(lib):
         "gm_learner_train": (i32, [vp, vp, vp, C.c_int64, i32, C.c_uint64, C.c_uint64, i32, C.c_float, i32, i32,
                                    C.c_float, vp]),
         "gm_ac_create": (i32,[vp, i32p, i32, i32p, i32, f32p, C.POINTER(vp)]),
+        "gm_ac_create_categorical": (i32,[vp, i32p, i32, i32p, i32, f32p, C.POINTER(vp)]),
+        "gm_ac_pack_categorical": (C.c_int64, [i32p, i32, i32p, i32, f32p, f32p, C.POINTER(C.c_int64)]),
         "gm_ac_destroy": (None, [vp]),
         "gm_ac_set_params": (i32, [vp, f32p]),
         "gm_ac_pack": (C.c_int64, [i32p, i32, i32p, i32, f32p, f32p, C.POINTER(C.c_int64)]),

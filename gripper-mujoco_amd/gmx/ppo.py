@@ -11,6 +11,10 @@ Mirrors the reference's policy-gradient rollout side:
 and its learner, Agent_PPO.optimise_model (:1440-1522): DevicePPOLearner runs compute_loss_pi's
 and compute_loss_v's backward, both Adam / AdamW optimisers and the KL stop on the device weights
 the rollout reads, so a training loop is ac.rollout(traj) followed by learner.update(traj).
+
+DeviceCategoricalActorCritic is the same for discrete actions: MLPActorCriticPG(continous_actions=
+False)'s MLPCategoricalActor (:429-447), whose outputs are logits and which has no log_std.  The
+buffer's action is then the chosen index as a float, TrajectoryBuffer(env, K, act_dim=1).
 """
 from __future__ import annotations
 
@@ -48,54 +52,67 @@ def noise_draws(seed, gids, decision, n_actions, noise: float) -> np.ndarray:
     return float(noise) * (2.0 * u3 - 1.0)
 
 
-def init_params(actor_sizes, critic_sizes, seed: int = 0) -> np.ndarray:
+def categorical_uniforms(seed, gids, decision) -> np.ndarray:
+    """The categorical sampler's one uniform u in [0, 1) per env (float64, exact: 24 bits) for
+    global env ids `gids` at one decision index: csrc/gm_ac_net.h ga_sample_cat's (c >> 40) / 2^24
+    with c = mix(h + 1), h the eps-greedy key.  The device takes the first j whose running sum of
+    e_j = exp(x_j - max x) exceeds u * sum e."""
+    return (_counters(seed, gids, decision, 1, 1)[:, 0] >> np.uint64(40)).astype(np.float64) / 16777216.0
+
+
+def init_params(actor_sizes, critic_sizes, seed: int = 0, categorical: bool = False) -> np.ndarray:
     """nn.Linear's default init for both nets and log_std = -0.5, flattened: the actor's W0
-    [out x in], b0, W1, b1, ..., the critic's likewise, then log_std."""
+    [out x in], b0, W1, b1, ..., the critic's likewise, then log_std (categorical: no log_std)."""
     rng = np.random.default_rng(seed)
     parts = linear_init(rng, actor_sizes) + linear_init(rng, critic_sizes)
-    parts.append(np.full(actor_sizes[-1], LOG_STD_INIT, dtype=np.float32))
+    if not categorical:
+        parts.append(np.full(actor_sizes[-1], LOG_STD_INIT, dtype=np.float32))
     return np.concatenate(parts).astype(np.float32)
 
 
 def params_from_state_dict(state_dict):
     """(actor_sizes, critic_sizes, flat params) from an MLPActorCriticPG state dict: pi.log_std,
-    pi.mu_net.{0,2,..}.weight / .bias, vf.v_net.{0,2,..}.weight / .bias."""
+    pi.mu_net.{0,2,..}.weight / .bias, vf.v_net.{0,2,..}.weight / .bias; or a categorical one's
+    pi.logits_net.{0,2,..}.weight / .bias and vf.v_net.*, which has no log_std."""
     def net(prefix):
         ws = sorted((k for k in state_dict if k.startswith(prefix) and k.endswith(".weight")),
                     key=lambda k: int(k[len(prefix):].split(".")[0]))
         if not ws:
             raise KeyError(f"no {prefix}*.weight in the state dict")
         return state_dict_net(state_dict, ws)
-    asz, ap = net("pi.mu_net.")
+    categorical = any(k.startswith("pi.logits_net.") for k in state_dict)
+    asz, ap = net("pi.logits_net." if categorical else "pi.mu_net.")
     csz, cp = net("vf.v_net.")
-    log_std = as_f32(state_dict["pi.log_std"]).ravel()
-    return asz, csz, np.concatenate(ap + cp + [log_std]).astype(np.float32)
+    tail = [] if categorical else [as_f32(state_dict["pi.log_std"]).ravel()]
+    return asz, csz, np.concatenate(ap + cp + tail).astype(np.float32)
 
 
-def n_params(actor_sizes, critic_sizes) -> int:
+def n_params(actor_sizes, critic_sizes, categorical: bool = False) -> int:
     """Floats of the flat parameters (init_params' order) for these layer sizes."""
     return (sum(s[i + 1] * s[i] + s[i + 1] for s in (actor_sizes, critic_sizes) for i in range(len(s) - 1))
-            + actor_sizes[-1])
+            + (0 if categorical else actor_sizes[-1]))
 
 
-def pack(actor_sizes, critic_sizes, params):
-    """(packed blob, critic offset, log_std offset): the device layout (gm_ac_pack; testable
-    without a GPU).  Raises ValueError for unsupported sizes or a wrong parameter count."""
+def pack(actor_sizes, critic_sizes, params, categorical: bool = False):
+    """(packed blob, critic offset, log_std offset): the device layout (gm_ac_pack, or
+    gm_ac_pack_categorical, whose log_std offset is the blob's end; testable without a GPU).
+    Raises ValueError for unsupported sizes or a wrong parameter count."""
     lib = load_library()
+    fn = lib.gm_ac_pack_categorical if categorical else lib.gm_ac_pack
     a = np.ascontiguousarray(actor_sizes, dtype=np.int32)
     c = np.ascontiguousarray(critic_sizes, dtype=np.int32)
     pr = np.ascontiguousarray(params, dtype=np.float32).ravel()
     i32p, f32p = C.POINTER(C.c_int32), C.POINTER(C.c_float)
     off = (C.c_int64 * 2)()
-    n = lib.gm_ac_pack(a.ctypes.data_as(i32p), len(a), c.ctypes.data_as(i32p), len(c), pr.ctypes.data_as(f32p), None, off)
+    n = fn(a.ctypes.data_as(i32p), len(a), c.ctypes.data_as(i32p), len(c), pr.ctypes.data_as(f32p), None, off)
     if n < 0:
         raise ValueError("unsupported network sizes")
-    want = n_params([int(x) for x in a], [int(x) for x in c])
+    want = n_params([int(x) for x in a], [int(x) for x in c], categorical)
     if pr.size != want:
         raise ValueError(f"{want} parameters expected for these sizes, got {pr.size}")
     out = np.zeros(n, dtype=np.float32)
-    lib.gm_ac_pack(a.ctypes.data_as(i32p), len(a), c.ctypes.data_as(i32p), len(c), pr.ctypes.data_as(f32p),
-                   out.ctypes.data_as(f32p), off)
+    fn(a.ctypes.data_as(i32p), len(a), c.ctypes.data_as(i32p), len(c), pr.ctypes.data_as(f32p),
+       out.ctypes.data_as(f32p), off)
     return out, int(off[0]), int(off[1])
 
 
@@ -108,16 +125,18 @@ class AcTraj(C.Structure):
 
 class TrajectoryBuffer:
     """K env-steps of every env, as torch tensors on the env's device in gm_ac_traj's layout
-    (time-major: all envs of one env-step are contiguous)."""
+    (time-major: all envs of one env-step are contiguous).  act_dim: floats of one action, by
+    default the env's n_actions; 1 for a DeviceCategoricalActorCritic, whose action is the chosen
+    index (mu then holds the logits, [K, n_envs, n_actions] either way)."""
 
-    def __init__(self, env, K: int, keep_mu: bool = True):
+    def __init__(self, env, K: int, keep_mu: bool = True, act_dim: int | None = None):
         import torch
         self.env = env
         self.K = int(K)
         n, dev = env.n_envs, f"cuda:{env.device}"
         f = dict(dtype=torch.float32, device=dev)
         self.obs = torch.zeros((self.K, n, env.n_obs), **f)
-        self.act = torch.zeros((self.K, n, env.n_actions), **f)
+        self.act = torch.zeros((self.K, n, env.n_actions if act_dim is None else int(act_dim)), **f)
         self.logp = torch.zeros((self.K, n), **f)
         self.val = torch.zeros((self.K, n), **f)
         self.rew = torch.zeros((self.K, n), **f)
@@ -182,6 +201,10 @@ class DeviceActorCritic:
     """An MLPActorCriticPG (Gaussian actor, critic) bound to a BatchedGripperEnv with
     continuous actions."""
 
+    categorical = False
+    _create = "gm_ac_create"
+    _actor_prefix = "pi.mu_net."
+
     def __init__(self, env, hidden=DEFAULT_HIDDEN, params=None, seed: int = 0, hidden_v=None,
                  actor_sizes=None, critic_sizes=None):
         self.env = env
@@ -191,29 +214,40 @@ class DeviceActorCritic:
         self.critic_sizes = [int(x) for x in (critic_sizes or [env.n_obs, *hv, 1])]
         #: the last weights handed in from the host (the constructor's, set_params'); a
         #: DevicePPOLearner's steps do not reach it: get_params() returns the device's
-        self.params = (init_params(self.actor_sizes, self.critic_sizes, seed) if params is None
+        self.params = (init_params(self.actor_sizes, self.critic_sizes, seed, self.categorical) if params is None
                        else np.ascontiguousarray(params, np.float32).copy())
         self._p = C.c_void_p()
         if min(self.actor_sizes + self.critic_sizes) < 1 or len(self.actor_sizes) < 2 or len(self.critic_sizes) < 2:
             raise ValueError("layer sizes must be positive, with at least an input and an output")
-        want = n_params(self.actor_sizes, self.critic_sizes)
+        want = n_params(self.actor_sizes, self.critic_sizes, self.categorical)
         if self.params.ndim != 1 or self.params.size != want:      # (the library reads exactly this many)
             raise ValueError(f"{want} parameters expected for these sizes, got {self.params.size}")
         a = np.ascontiguousarray(self.actor_sizes, dtype=np.int32)
         c = np.ascontiguousarray(self.critic_sizes, dtype=np.int32)
         i32p = C.POINTER(C.c_int32)
-        rc = self.lib.gm_ac_create(env.ctx, a.ctypes.data_as(i32p), len(a), c.ctypes.data_as(i32p), len(c),
-                                   self.params.ctypes.data_as(C.POINTER(C.c_float)), C.byref(self._p))
+        rc = getattr(self.lib, self._create)(env.ctx, a.ctypes.data_as(i32p), len(a), c.ctypes.data_as(i32p), len(c),
+                                             self.params.ctypes.data_as(C.POINTER(C.c_float)), C.byref(self._p))
         if rc != 0:
-            raise RuntimeError(self.lib.gm_last_error(env.ctx).decode() or f"gm_ac_create failed ({rc})")
+            raise RuntimeError(self.lib.gm_last_error(env.ctx).decode() or f"{self._create} failed ({rc})")
 
     def _check(self, rc, what):
         if rc != 0:
             raise RuntimeError(self.lib.gm_last_error(self.env.ctx).decode() or f"{what} failed ({rc})")
 
+    def _traj_ok(self, traj, noise=0.0):
+        """The buffer's action width is this actor's (the library sees pointers only: a narrower
+        buffer would be read or written past its end)."""
+        want = 1 if self.categorical else self.env.n_actions
+        if traj.act.shape[-1] != want:
+            raise ValueError(f"a TrajectoryBuffer with act_dim = {want} expected, got {traj.act.shape[-1]}")
+        if self.categorical and noise != 0:
+            raise ValueError("a categorical actor takes no exploration noise (noise must be 0)")
+
     def set_params(self, params):
         """New weights after a learner update (flat, init_params' order, or a state dict)."""
         if isinstance(params, dict):
+            if any(k.startswith("pi.logits_net.") for k in params) != self.categorical:
+                raise ValueError("state dict of the other actor class (pi.mu_net / pi.logits_net)")
             asz, csz, params = params_from_state_dict(params)
             if asz != self.actor_sizes or csz != self.critic_sizes:
                 raise ValueError("state dict does not match the network sizes")
@@ -232,7 +266,7 @@ class DeviceActorCritic:
 
     def get_packed(self) -> np.ndarray:
         """The device's weights as stored (pack()'s layout, padding entries included)."""
-        out = np.empty(pack(self.actor_sizes, self.critic_sizes, self.params)[0].size, dtype=np.float32)
+        out = np.empty(pack(self.actor_sizes, self.critic_sizes, self.params, self.categorical)[0].size, dtype=np.float32)
         self._check(self.lib.gm_ac_get_packed(self._p, out.ctypes.data_as(C.POINTER(C.c_float))), "gm_ac_get_packed")
         return out
 
@@ -241,19 +275,21 @@ class DeviceActorCritic:
         .weight / .bias, vf.v_net.{0,2,..}.weight / .bias) as numpy arrays: what
         params_from_state_dict and set_params read."""
         flat, pos, out = self.get_params(), 0, {}
-        for prefix, sizes in (("pi.mu_net.", self.actor_sizes), ("vf.v_net.", self.critic_sizes)):
+        for prefix, sizes in ((self._actor_prefix, self.actor_sizes), ("vf.v_net.", self.critic_sizes)):
             for l in range(len(sizes) - 1):
                 fin, fout = sizes[l], sizes[l + 1]
                 out[f"{prefix}{2 * l}.weight"] = flat[pos:pos + fout * fin].reshape(fout, fin).copy()
                 pos += fout * fin
                 out[f"{prefix}{2 * l}.bias"] = flat[pos:pos + fout].copy()
                 pos += fout
-        out["pi.log_std"] = flat[pos:].copy()
+        if not self.categorical:
+            out["pi.log_std"] = flat[pos:].copy()
         return out
 
     def act(self, traj: TrajectoryBuffer, k: int, sample: bool = True, noise: float = 0.0, seed: int = 0,
             decision: int = 0):
         """select_action for every env from its current observation into row k, applied on the device."""
+        self._traj_ok(traj, noise)
         t = traj.struct()
         self._check(self.lib.gm_ac_act(self._p, C.byref(t), int(k), int(bool(sample)), C.c_float(noise),
                                        C.c_uint64(seed), C.c_uint64(decision)), "gm_ac_act")
@@ -277,6 +313,7 @@ class DeviceActorCritic:
         per-step sequence).  records_dev_ptr: device [n_steps x n_envs] gm_episode_end records."""
         n = traj.K - k0 if n_steps is None else int(n_steps)
         mx = self.env.max_episode_steps if max_episode_steps is None else max_episode_steps
+        self._traj_ok(traj, noise)
         t = traj.struct(k0)
         self._check(self.lib.gm_ac_rollout(self._p, C.byref(t), n, int(bool(sample)), C.c_float(noise), C.c_uint64(seed),
                                            C.c_uint64(decision0), int(mx), C.c_void_p(records_dev_ptr or 0)),
@@ -295,6 +332,18 @@ class DeviceActorCritic:
             self.close()
         except Exception:
             pass
+
+
+class DeviceCategoricalActorCritic(DeviceActorCritic):
+    """An MLPActorCriticPG(continous_actions=False) (categorical actor, critic) bound to a
+    BatchedGripperEnv with discrete actions: the actor's outputs are logits, there is no log_std,
+    the state dict's actor keys are pi.logits_net.*, the buffer is TrajectoryBuffer(env, K,
+    act_dim=1) (the chosen index as a float; mu holds the logits) and noise must be 0.  sample=False
+    takes the argmax.  Everything else, DevicePPOLearner included, is DeviceActorCritic's."""
+
+    categorical = True
+    _create = "gm_ac_create_categorical"
+    _actor_prefix = "pi.logits_net."
 
 
 _OPTIMISERS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW}
@@ -365,7 +414,7 @@ class DevicePPOLearner:
         tensors under those keys); the tensors named in `keys` are checked and passed."""
         import torch
         n = int(data["obs"].shape[0])
-        want = dict(obs=(n, self.env.n_obs), act=(n, self.env.n_actions), logp=(n,), adv=(n,), ret=(n,))
+        want = dict(obs=(n, self.env.n_obs), act=(n, 1 if self.ac.categorical else self.env.n_actions), logp=(n,), adv=(n,), ret=(n,))
         b = PpoBatch()
         b.n = n
         for k in keys:
@@ -439,6 +488,7 @@ class DevicePPOLearner:
         import torch
         h = self._handle()
         k = traj.K if n_steps is None else int(n_steps)
+        self.ac._traj_ok(traj)
         t = traj.struct()
         info = PpoInfo()
         torch.cuda.synchronize(traj.obs.device)     # torch-side writes to the buffers (tests)

@@ -860,14 +860,15 @@ typedef struct gm_ac_traj {
   int32_t capacity;   /* env-steps K the arrays hold */
   int32_t pad;
   float*   obs;       /* [K][n_envs][n_obs]   observation the action was chosen from */
-  float*   act;       /* [K][n_envs][n_actions] action sent to the env (noisy, unclipped) */
+  float*   act;       /* [K][n_envs][n_actions] action sent to the env (noisy, unclipped);
+                         categorical handle: [K][n_envs][1], the chosen index as a float */
   float*   logp;      /* [K][n_envs] */
   float*   val;       /* [K][n_envs]  V(obs[k]) */
   float*   rew;       /* [K][n_envs]  reward of env-step k */
   uint8_t* end;       /* [K][n_envs]  0 episode continues, 1 terminal (done), 2 truncated only */
   float*   boot;      /* [K][n_envs]  V(observation after env-step k) where end == 2, else 0 */
   float*   last_val;  /* [n_envs]     V(observation after the last recorded env-step) */
-  float*   mu;        /* [K][n_envs][n_actions], may be NULL (diagnostics / tests) */
+  float*   mu;        /* [K][n_envs][n_actions], may be NULL (diagnostics / tests); categorical: the logits */
 } gm_ac_traj;
 typedef struct gm_ac gm_ac;
 /* actor_sizes: [n_obs, hidden..., n_actions]; critic_sizes: [n_obs, hidden..., 1]; params (host,
@@ -923,6 +924,31 @@ int  gm_ac_get_params(gm_ac* p, float* flat);
  * included, which must stay exactly 0 under every update. */
 int  gm_ac_get_packed(gm_ac* p, float* packed);
 
+/* ---- the categorical actor: PPO on discrete actions ----
+ * MLPActorCriticPG(continous_actions=False) builds an MLPCategoricalActor (PolicyGradient.py:429-447,
+ * :504-509): the same MLP [n_obs, hidden..., n_actions] with its outputs read as logits,
+ *   pi = Categorical(logits = logits_net(obs)),  a ~ pi,  logp = pi.log_prob(a) = logits_a - logsumexp
+ * and no log_std.  params: the actor's W0, b0, ..., then the critic's; the blob is [actor | critic].
+ * Needs continous_actions == 0; GM_E_ARG with a gm_last_error message otherwise, and for an actor
+ * that does not map n_obs to gm_n_actions or a critic that does not map n_obs to 1.
+ * The handle is a gm_ac: every gm_ac_* and gm_ppo_learner_* call takes it.  With it
+ *   gm_ac_traj.act is [K][n_envs][1], the chosen index as a float (PPOBuffer with action_dim 1);
+ *   gm_ac_traj.mu, when non-NULL, holds the logits [K][n_envs][n_actions];
+ *   gm_ppo_batch.act is [n][1];
+ *   noise != 0 is GM_E_ARG (the reference's select_action adds float noise in place to a Long
+ *   tensor, which raises: the categorical actor runs with use_random_action_noise = False only);
+ *   gm_ac_act applies the index through the discrete-action path, as gm_policy_act does, the
+ *   termination action's extra substeps included;  sample = 0 takes the argmax (lowest index on a tie);
+ *   the learner's ent is the mean row entropy, its gradient goes through the logits, and the
+ *   optimiser state calls carry no log_std entries.
+ * One uniform per (seed, global env id, decision) picks the action by the inverse CDF
+ * (csrc/gm_ac_net.h ga_sample_cat; gmx/ppo.py categorical_uniforms mirrors the draw). */
+int  gm_ac_create_categorical(gm_ctx* ctx, const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes,
+                              int n_critic, const float* params, gm_ac** out);
+/* gm_ac_pack without log_std: off2[1] is then the packed count itself. */
+int64_t gm_ac_pack_categorical(const int32_t* actor_sizes, int n_actor, const int32_t* critic_sizes,
+                               int n_critic, const float* params, float* out, int64_t* off2);
+
 /* ---- PPO learner: clipped-surrogate backward, two Adams, KL stop ----
  * Agent_PPO.optimise_model (rl/agents/PolicyGradient.py:1440-1522) on the packed weights where the
  * rollout reads them: gradients and moments live in gm_ac_pack's layout, the steps update the
@@ -952,7 +978,7 @@ void gm_ppo_opt_default(gm_ppo_opt* out);
 typedef struct gm_ppo_batch {
   int64_t n;
   const float* obs;             /* [n][n_obs] */
-  const float* act;             /* [n][n_actions] */
+  const float* act;             /* [n][n_actions]; categorical handle: [n][1], the index as a float */
   const float* logp;            /* [n]  log-probabilities under the policy that collected the rows */
   const float* adv;             /* [n]  (normalised) advantages */
   const float* ret;             /* [n]  rewards-to-go */
