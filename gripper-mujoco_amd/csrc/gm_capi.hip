@@ -299,10 +299,12 @@ int build_topo(const gm_model& m, GmTopo& T, std::string& err) {
   if (T.CL > 15) { err = "finger chain longer than a 16-lane DPP row"; return GM_E_RANGE; }
   for (int f = 0; f < 3; f++)
     for (int p = 1; p <= T.CL; p++) T.lane_body[16 * f + p] = T.body_f0[f] + p - 1;
-  T.lane_base = 48;
-  T.lane_body[48] = T.body_base;
-  T.lane_body[49] = T.body_palm;
-  T.lane_body[50] = T.body_obj;
+  T.lane_base = GM_LANE_BASE;
+  T.lane_body[GM_LANE_BASE] = T.body_base;
+  T.lane_body[GM_LANE_BASE + 1] = T.body_palm;
+  T.lane_body[GM_LANE_BASE + 2] = T.body_obj;
+  for (int l = GM_OBJ_LANE0; l < GM_OBJ_LANE0 + 6; l++)   // (gm_shared.h asserts the layout)
+    if (T.lane_body[l] >= 0) { err = "a body's scan lane on the object's component lanes"; return GM_E_RANGE; }
   // per-dof constants: the engine-spec H~ diagonal additions and PD gains
   // (mj_step2 implicit damping / PD terms and luke::control gains, oracle.c ctrl_gains / step2)
   for (int d = 0; d < m.nv; d++) {

@@ -1,7 +1,8 @@
 // gm_dynamics.h -- physics stage 1, the smooth dynamics: mj_kinematics (oracle.c fk), mj_rne /
 // mj_crb, the H~ rows and the smooth force per dof (with the calibration tip load,
 // myfunctions.cpp:1642-1727).  SharedT: reads s.qpos, s.qvel, s.next, s.base; writes xpos, xquat,
-// cdof, cinert / Ic, cfrc, chain_f, chain_I, Hf, Hp, Ho, Hbb, frc (and lock_rows' lrow_*, nl).
+// cdof, cinert / Ic, cfrc, chain_f, chain_I, Hf, Hp, Ho, Hbb, frc (and lock_rows' lrow_*, nl;
+// crb_rne hands the object's three cross products over in go, dead until the Newton point).
 #pragma once
 #include "gm_real.h"
 #include "gm_rows.h"
@@ -318,6 +319,51 @@ __device__ __forceinline__ void crb_rne(SharedT<CL>& S, const gm_model* __restri
       for (int k = 0; k < 10; k++) S.chain_I[grp][k] = ci[k];
     }
   }
+#ifndef GM_NO_OBJECT_LANES
+  {
+    // object: free joint on one body.  Its velocity and bias-acceleration sums run one
+    // component t per lane on lanes GM_OBJ_LANE0 + t and the three cross_motion one rotation
+    // dof k per lane on lanes GM_OBJ_LANE0 + k, each sum in the one-lane loop's order (from
+    // +0 / the gravity term, k = 0 .. 2); every lane issues them on a clamped index, so there
+    // is no divergent branch, and only those six lanes are read.  cvel after the translations
+    // reaches the cross products by readlane, their 18 results change lanes through S.go
+    // (dead between two Newton points), and the finished cvel / cacc reach body_force as
+    // wave-uniform operands.
+    const int d0 = T->dof_obj;
+    const int ol = lane - GM_OBJ_LANE0;
+    const int t = ol < 0 ? 0 : (ol > 5 ? 5 : ol);
+    const int kr = t < 3 ? t : 2;
+    real qv[6], cdt[6], cdk[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) { qv[k] = S.s.qvel[d0 + k]; cdt[k] = S.cdof[d0 + k][t]; cdk[k] = S.cdof[d0 + 3 + kr][k]; }
+    real cvt = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) cvt += cdt[k] * qv[k];
+    real cw[6], cdd[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) cw[k] = readlane_real(cvt, GM_OBJ_LANE0 + k);
+    cross_motion(cdd, cw, cdk);
+    if (ol >= 0 && ol < 3) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) S.go[6 * ol + k] = cdd[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) cvt += cdt[3 + k] * qv[3 + k];
+    GM_WAVE_SYNC();
+    real cat = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) cat = (t == 3 + k) ? -(real)m->gravity[k] : cat;
+#pragma unroll
+    for (int k = 0; k < 3; k++) cat += S.go[6 * k + t] * qv[3 + k];
+    real cvel[6], cacc[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      cvel[k] = readlane_real(cvt, GM_OBJ_LANE0 + k);
+      cacc[k] = readlane_real(cat, GM_OBJ_LANE0 + k);
+    }
+    if (b == T->body_obj) body_force(S, b, cvel, cacc);
+  }
+#else
   if (b == T->body_obj) {
     // object: free joint on one body
     const int d0 = T->dof_obj;
@@ -348,6 +394,7 @@ __device__ __forceinline__ void crb_rne(SharedT<CL>& S, const gm_model* __restri
     }
     body_force(S, b, cvel, cacc);
   }
+#endif
   GM_WAVE_SYNC();
   PH(17);
   // base body: its own inertia / force plus the four chain roots, one lane per value

@@ -132,8 +132,8 @@ __device__ __forceinline__ void euler_solve(SharedT<CL>& S, const GmTopo* __rest
     S.xs[T->dof_palm] = S.qacc[T->dof_palm] - y;
   } else if (lane == 48) {
     S.xs[db] = S.qacc[db] - xb;
-  } else if (lane >= 57 && lane < 63) {
-    const int d = T->dof_obj + lane - 57;
+  } else if (lane >= GM_OBJ_LANE0 && lane < GM_OBJ_LANE0 + 6) {
+    const int d = T->dof_obj + lane - GM_OBJ_LANE0;
     S.xs[d] = res ? S.qacc[d] - S.Mv[d] : S.qacc[d];
   }
   GM_WAVE_SYNC();

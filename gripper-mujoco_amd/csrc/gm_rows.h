@@ -87,6 +87,30 @@ __device__ void body_vel(SharedT<CL>& S, const real* const* v, real (*const* V)[
     for (int n = 0; n < NVEC; n++)
 #pragma unroll
       for (int k = 0; k < 6; k++) V[n][T->body_base][k] = cvb[n][k];
+#ifndef GM_NO_OBJECT_LANES
+  } else if (lane >= GM_OBJ_LANE0 && lane < GM_OBJ_LANE0 + 6) {
+    // the object's free joint, one component per lane (the lanes euler_solve gives the
+    // object dofs; gm_shared.h asserts that they hold no chain link, base, palm or object,
+    // so the branches above never take them): component t sums its six products from +0
+    // in dof order, the one-lane loop's additions for that component, operand for operand
+    const int d0 = T->dof_obj, t = lane - GM_OBJ_LANE0;
+    real co[6], vk[NVEC][6], acc[NVEC];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      co[k] = S.cdof[d0 + k][t];
+#pragma unroll
+      for (int n = 0; n < NVEC; n++) vk[n][k] = v[n][d0 + k];
+    }
+    keep_n<6>(co);
+#pragma unroll
+    for (int n = 0; n < NVEC; n++) acc[n] = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+#pragma unroll
+      for (int n = 0; n < NVEC; n++) acc[n] += co[k] * vk[n][k];
+#pragma unroll
+    for (int n = 0; n < NVEC; n++) V[n][T->body_obj][t] = acc[n];
+#else
   } else if (b == T->body_obj) {
     const int d0 = T->dof_obj;
     real acc[NVEC][6];
@@ -116,6 +140,7 @@ __device__ void body_vel(SharedT<CL>& S, const real* const* v, real (*const* V)[
     for (int n = 0; n < NVEC; n++)
 #pragma unroll
       for (int t = 0; t < 6; t++) V[n][b][t] = acc[n][t];
+#endif
   } else if (lane == 0) {
 #pragma unroll
     for (int n = 0; n < NVEC; n++)

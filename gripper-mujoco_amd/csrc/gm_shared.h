@@ -65,6 +65,13 @@ __device__ __forceinline__ void keep_n(const double* a) {
 #define TRIF ((CLMAX + 1) * (CLMAX + 2) / 2)
 #define CW (CL + 8)   // compact row: obj[6], base, chain[CL] (+1 scratch slot); needs CL in scope
 #define PI_F 3.14159265358979f
+// lanes GM_OBJ_LANE0 .. + 5: the object's six dofs / velocity components, one per lane.  They
+// lie past every scan lane (GmTopo::lane_body: finger f's links on lanes 16 f + 1 .. 16 f + CL,
+// base, palm and object on GM_LANE_BASE .. + 2) and are not lane 0.
+#define GM_LANE_BASE 48
+#define GM_OBJ_LANE0 57
+static_assert(32 + CLMAX < GM_LANE_BASE && GM_LANE_BASE + 2 < GM_OBJ_LANE0 && GM_OBJ_LANE0 + 6 <= 64,
+              "the object's component lanes must hold no body's scan lane");
 
 // `real` is the dynamics type: fp64, MuJoCo's mjtNum.  Kinematics, dynamics, collision
 // geometry and the PGS solve all run in it (see DESIGN.md "Precision").

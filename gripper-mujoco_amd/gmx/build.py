@@ -28,14 +28,26 @@ def _deps():
         [os.path.join(REPO_DIR, "include", f) for f in ("gripper_mi355x.h", "gm_settings.def")]
 
 
-def build_no_decoupled(verbose: bool = False) -> str:
-    """build(out=NO_DECOUPLED_LIB, extra_flags=["-DGM_NO_DECOUPLED_POINT"]), unless that
-    library is already newer than every source."""
-    if os.path.exists(NO_DECOUPLED_LIB):
-        t = os.path.getmtime(NO_DECOUPLED_LIB)
+def _build_variant(lib: str, flag: str, verbose: bool) -> str:
+    """build(out=lib, extra_flags=[flag]), unless that library is already newer than every source."""
+    if os.path.exists(lib):
+        t = os.path.getmtime(lib)
         if all(os.path.getmtime(d) <= t for d in _deps()):
-            return NO_DECOUPLED_LIB
-    return build(verbose=verbose, out=NO_DECOUPLED_LIB, extra_flags=["-DGM_NO_DECOUPLED_POINT"])
+            return lib
+    return build(verbose=verbose, out=lib, extra_flags=[flag])
+
+
+def build_no_decoupled(verbose: bool = False) -> str:
+    return _build_variant(NO_DECOUPLED_LIB, "-DGM_NO_DECOUPLED_POINT", verbose)
+
+
+# ... and with the free object's velocity sums back on one lane
+# (csrc/gm_rows.h, gm_dynamics.h): the partner of tests/test_object_lanes.py
+NO_OBJECT_LANES_LIB = os.path.join(os.path.dirname(LIB_PATH), "libgm_no_object_lanes.so")
+
+
+def build_no_object_lanes(verbose: bool = False) -> str:
+    return _build_variant(NO_OBJECT_LANES_LIB, "-DGM_NO_OBJECT_LANES", verbose)
 
 
 def build(verbose: bool = False, force: bool = False, out: str | None = None, extra_flags=()) -> str:
