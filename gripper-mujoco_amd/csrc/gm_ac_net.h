@@ -60,6 +60,7 @@ struct GaArgs {
   int sample;                   // 0: a = mu (categorical: the argmax)
   float noise;
   uint64_t seed, decision0;     // env-step k of the launch draws with decision0 + k
+  int one_row, pad;             // != 0 (gm_ac_evaluate): every env-step of the launch writes trajectory row 0
 };
 
 // Sampling and log-probability for ONE env on ONE lane (the batched kernel and the rollout

@@ -37,6 +37,11 @@ hipError_t gm_cal_launch_read(hipStream_t st, const GmEnvState* states, uint8_t*
 hipError_t gm_cal_launch_gauge(int n_seg, hipStream_t st, const GmEnvState* states, const gm_model* m, const GmTopo* T,
                                int env, float* out);
 
+// evaluation translation unit (gm_eval.hip): the evaluation launch's kernel instantiations
+hipError_t gm_eval_launch_step(int n_seg, bool duo, int grid, hipStream_t st, GmEnvState* states, const gm_model* m,
+                               const gm_config* C, const GmTopo* T, float* obs, float* rew, uint8_t* done, int n_envs,
+                               const int32_t* order, uint32_t* cost, const GmChunkQ& q);
+
 // Move-only owner of one hipMalloc allocation of T (Pinned: of one hipHostMalloc allocation): the
 // only code of this file that allocates or frees device or pinned memory.  It reads as the raw
 // pointer wherever one is expected; a copy of that pointer is a view and frees nothing.
@@ -103,6 +108,7 @@ struct gm_ctx {
   hipEvent_t stage_ev = nullptr;
   DevBuf<int32_t> d_dact;
   DevBuf<uint8_t> d_mask;
+  DevBuf<uint8_t> d_eval_active;       // the per-step evaluation's working copy of the caller's active bytes
   // scratch of the force-measurement calls (gm_set_motor_target's targets and flags,
   // gm_get_sensor_si's readings): allocated once with the context, no per-call allocation
   // (freeing one synchronises the whole device)
@@ -191,8 +197,10 @@ bool nseg_supported(int n) {
     default: return false;
   }
 }
-// job: a rollout's (rollout_job; it needs the chunked queue), NULL: one plain env-step per env
-hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, const GmRolloutJob* job = nullptr) {
+// job: a rollout's (rollout_job; it needs the chunked queue), NULL: one plain env-step per env;
+// eval: the job is an evaluation's (eval_launch), run by gm_eval.hip's instantiations
+hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, const GmRolloutJob* job = nullptr,
+                       bool eval = false) {
   // the full env-step (mode 0) runs in cost-sorted order and records each env's cost
   const int32_t* order = (mode == 0 && grid == c->n_envs) ? c->d_order.get() : nullptr;
   uint32_t* cost = (mode == 0 && grid == c->n_envs) ? c->d_cost.get() : nullptr;
@@ -208,6 +216,10 @@ hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, 
   // the env-step proper (not the settle, a diagnostic substep or a profiled step) on DUO
   // workgroups when the context chose them; the chunked grid was sized for that kernel
   const bool duo = c->duo && mode == 0;   // (a profiled step too: the owner wave's phase clocks)
+  if (eval)
+    return job && chunked ? gm_eval_launch_step(c->model.n_seg, duo, grid, c->stream, c->d_state, c->d_model, c->d_cfg,
+                                                c->d_topo, c->d_obs, c->d_rew, c->d_done, n_envs, order, cost, q)
+                          : hipErrorInvalidValue;
   switch (c->model.n_seg) {
 #define X(N)                                                                                                 \
   case N:                                                                                                    \
@@ -227,10 +239,10 @@ hipError_t launch_step(gm_ctx* c, int grid, int n_envs, int mode, DebugOut dbg, 
 }
 // The timed env-step launch (gm_step, and the rollouts' one persistent launch of job->steps
 // env-steps per env) and the next launch's dispatch order
-int timed_launch(gm_ctx* c, const GmRolloutJob* job) {
+int timed_launch(gm_ctx* c, const GmRolloutJob* job, bool eval = false) {
   DebugOut dbg{nullptr, nullptr, nullptr, nullptr, nullptr};
   HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  HIPCHK(c, launch_step(c, c->n_envs, c->n_envs, 0, dbg, job));
+  HIPCHK(c, launch_step(c, c->n_envs, c->n_envs, 0, dbg, job, eval));
   HIPCHK(c, hipEventRecord(c->ev1, c->stream));
   hipLaunchKernelGGL(gm_dispatch_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_cost, c->d_order, c->n_envs,
                      c->d_chunk_ctr, c->d_chunk_st);
@@ -258,6 +270,55 @@ int per_step_rollout(gm_ctx* c, int n_steps, int max_ep, gm_episode_end* records
     if (rc == GM_OK) rc = after(k);
     if (rc == GM_OK) rc = gm_autoreset_episodes(c, max_ep, nullptr, 1, nullptr,
                                                 records ? records + (size_t)k * c->n_envs : nullptr);
+    if (rc != GM_OK) return rc;
+  }
+  return GM_OK;
+}
+// An agent's evaluation needs the action kind its handle was created for (gm_policy_create's,
+// gm_ac_create's and gm_sac_create's rule, here for a config that gm_update_config changed since:
+// the network's outputs would no longer be the env's actions)
+int eval_action_kind(gm_ctx* c, const char* who, bool continuous, const char* agent) {
+  if ((c->cfg.s.continous_actions != 0) == continuous) return GM_OK;
+  return fail(c, GM_E_ARG, std::string(who) + ": " + agent + " needs " + (continuous ? "continuous" : "discrete") +
+                               " actions (continous_actions " + (continuous ? "!= 0)" : "= 0)"));
+}
+// An evaluation entry point (gm_evaluate and the like; who: its name): the checks they share ...
+int eval_check(gm_ctx* c, const char* who, int max_ep, const gm_eval_out* out) {
+  if (max_ep <= 0)
+    return fail(c, GM_E_ARG, std::string(who) + ": max_episode_steps must be positive (the launch would be unbounded)");
+  if (!out || !out->ret || !out->length || !out->end || !out->rows || !out->abs || !out->last)
+    return fail(c, GM_E_ARG, std::string(who) + ": no report arrays, or one of ret, length, end, rows, abs, last missing");
+  return GM_OK;
+}
+// ... the job as one persistent launch when the queue is on: every active env runs until its
+// episode ends (at most job.steps = max_episode_steps env-steps), reports and retires ...
+int eval_launch(gm_ctx* c, GmRolloutJob job, const uint8_t* active, const gm_eval_out* out) {
+  job.rec = nullptr;
+  job.active = active;
+  job.ev = *out;
+  return timed_launch(c, &job, true);
+}
+hipError_t launch_eval_record(gm_ctx* c, int max_ep, uint8_t* active, const gm_eval_out* out, int init) {
+  hipLaunchKernelGGL(gm_eval_record_kernel, dim3(c->n_envs), dim3(64), 0, c->stream, c->d_state.get(), c->d_done,
+                     max_ep, active, *out, c->n_envs, init);
+  return hipGetLastError();
+}
+// ... and with the one-shot kernel as the per-step sequence the launch fuses, max_ep times: the
+// driver's before(k) -> gm_step -> gm_eval_record -> gm_autoreset_episodes, on the context's own
+// copy of the active bytes (envs that have reported carry on into later episodes, ignored)
+template <class Before>
+int per_step_evaluate(gm_ctx* c, int max_ep, const uint8_t* active, const gm_eval_out* out, Before before) {
+  if (active)
+    HIPCHK(c, hipMemcpyAsync(c->d_eval_active, active, (size_t)c->n_envs, hipMemcpyDeviceToDevice, c->stream));
+  else
+    HIPCHK(c, hipMemsetAsync(c->d_eval_active, 1, (size_t)c->n_envs, c->stream));
+  HIPCHK(c, launch_eval_record(c, max_ep, c->d_eval_active, out, 1));
+  for (int k = 0; k < max_ep; k++) {
+    int rc = before(k);
+    if (rc == GM_OK) rc = gm_step(c);
+    if (rc != GM_OK) return rc;
+    HIPCHK(c, launch_eval_record(c, max_ep, c->d_eval_active, out, 0));
+    rc = gm_autoreset_episodes(c, max_ep, nullptr, 1, nullptr, nullptr);
     if (rc != GM_OK) return rc;
   }
   return GM_OK;
@@ -508,6 +569,7 @@ int gm_create(const gm_model* model, const gm_config* cfg, const gm_object* obje
   HIPCHK(c, c->d_act.alloc((size_t)n_envs * GM_ACTION_CODE_COUNT));
   HIPCHK(c, c->d_dact.alloc((size_t)n_envs));
   HIPCHK(c, c->d_mask.alloc((size_t)n_envs));
+  HIPCHK(c, c->d_eval_active.alloc((size_t)n_envs));
   HIPCHK(c, c->d_spawn.alloc((size_t)n_envs));
   HIPCHK(c, c->d_order.alloc((size_t)n_envs));
   // two halves: [0, n) the costs the current launch is ordered and scheduled by (read-only
@@ -788,6 +850,33 @@ int gm_rollout(gm_ctx* c, int n_steps, const gm_rollout_params* p, gm_episode_en
         return rc == GM_OK ? gm_set_action(c, c->d_act, 1) : rc;
       },
       [](int) { return (int)GM_OK; });
+}
+
+int gm_eval_record(gm_ctx* c, int max_episode_steps, uint8_t* active_inout, const gm_eval_out* out) {
+  if (!c) return GM_E_ARG;
+  const int rc = eval_check(c, "gm_eval_record", max_episode_steps, out);
+  if (rc != GM_OK) return rc;
+  if (!active_inout) return fail(c, GM_E_ARG, "gm_eval_record: no active bytes");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, launch_eval_record(c, max_episode_steps, active_inout, out, 0));
+  return GM_OK;
+}
+
+int gm_evaluate(gm_ctx* c, const gm_rollout_params* p, const uint8_t* active, const gm_eval_out* out) {
+  if (!c) return GM_E_ARG;
+  if (!p || (p->action_mode != GM_DRV_SCRIPT && p->action_mode != GM_DRV_RANDOM && p->action_mode != GM_DRV_PROGRAM &&
+             p->action_mode != GM_DRV_MIX))
+    return fail(c, GM_E_ARG, "gm_evaluate: no parameters, or an action_mode other than 0, 1, 3 or 4");
+  const int rc = eval_check(c, "gm_evaluate", p->max_episode_steps, out);
+  if (rc != GM_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (chunk_queue_on(c))
+    return eval_launch(c, rollout_job(c, p->max_episode_steps, (GmDriver)p->action_mode, p->seed, p->jitter,
+                                      p->max_episode_steps, nullptr), active, out);
+  return per_step_evaluate(c, p->max_episode_steps, active, out, [&](int) {
+    const int r = driver_actions_out(c, p->action_mode, p->seed, p->jitter, c->d_act, 1);
+    return r == GM_OK ? gm_set_action(c, c->d_act, 1) : r;
+  });
 }
 
 int gm_set_random_spawn(gm_ctx* c, int enable, uint64_t seed, int position_noise_mm, int rotation_noise_deg) {
@@ -1478,6 +1567,34 @@ int gm_policy_rollout(gm_policy* p, int n_steps, const float* eps, uint64_t seed
   return policy_rollout(p, n_steps, eps, seed, decision0, max_episode_steps, records, nullptr, 0);
 }
 
+int gm_policy_evaluate(gm_policy* p, uint64_t seed, uint64_t decision0, int max_episode_steps, const uint8_t* active,
+                       const gm_eval_out* out) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  int rc = eval_action_kind(c, "gm_policy_evaluate", false, "the DQN policy");
+  if (rc == GM_OK) rc = eval_check(c, "gm_policy_evaluate", max_episode_steps, out);
+  if (rc != GM_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (chunk_queue_on(c)) {
+    if (max_episode_steps > p->eps_cap) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));   // (the stream may still read the old buffer)
+      p->eps_cap = 0;
+      HIPCHK(c, p->d_eps.alloc((size_t)max_episode_steps));
+      p->eps_cap = max_episode_steps;
+    }
+    // greedy: the exploration threshold of every env-step is 0
+    HIPCHK(c, hipMemsetAsync(p->d_eps, 0, sizeof(float) * (size_t)max_episode_steps, c->stream));
+    GmRolloutJob job = rollout_job(c, max_episode_steps, GM_DRV_DQN, seed, 0.0f, max_episode_steps, nullptr);
+    job.pparams = p->d_params;
+    job.pnet = p->net;
+    job.peps = p->d_eps;
+    job.pdecision = decision0;
+    return eval_launch(c, job, active, out);
+  }
+  return per_step_evaluate(c, max_episode_steps, active, out,
+                           [&](int k) { return gm_policy_act(p, 0.0f, seed, decision0 + (uint64_t)k); });
+}
+
 int gm_policy_push_begin(gm_policy* p, const gm_replay* replay, int64_t row0) {
   return policy_push(p, replay, row0, 0, true);
 }
@@ -1832,6 +1949,10 @@ struct gm_ac {
   std::vector<int32_t> asz, csz;
   DevBuf<float> d_params;
   DevBuf<GaArgs> d_args;       // gm_ac_rollout's launch arguments
+  // gm_ac_evaluate's one-row scratch trajectory (made at its first call): the float rows obs,
+  // act, mu, logp, val, rew, boot, last_val in one allocation, and the end bytes
+  DevBuf<float> d_eval_rows;
+  DevBuf<uint8_t> d_eval_end;
 };
 
 static_assert(GA_MAX_ACT >= GM_ACTION_CODE_COUNT, "the sampler's rows hold every action");
@@ -2018,6 +2139,47 @@ int gm_ac_rollout(gm_ac* p, const gm_ac_traj* traj, int n_steps, int sample, flo
       [&](int k) { return gm_ac_act(p, traj, k, sample, noise, seed, decision0 + (uint64_t)k); },
       [&](int k) { return gm_ac_record(p, traj, k, max_episode_steps); });
   return rc == GM_OK ? gm_ac_finish(p, traj, n_steps - 1) : rc;
+}
+
+int gm_ac_evaluate(gm_ac* p, int sample, uint64_t seed, uint64_t decision0, int max_episode_steps,
+                   const uint8_t* active, const gm_eval_out* out) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  int rc = eval_action_kind(c, "gm_ac_evaluate", !p->net.categorical,
+                            p->net.categorical ? "the categorical actor" : "the Gaussian actor");
+  if (rc == GM_OK) rc = eval_check(c, "gm_ac_evaluate", max_episode_steps, out);
+  if (rc != GM_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_envs, n_obs = (size_t)c->cfg.n_obs, na = (size_t)c->cfg.n_actions;
+  if (!p->d_eval_rows) {
+    HIPCHK(c, p->d_eval_rows.alloc(n * (n_obs + 2 * na + 5)));
+    HIPCHK(c, p->d_eval_end.alloc(n));
+  }
+  // the actor's phases write one trajectory row whatever the env-step: nothing of it is kept
+  float* f = p->d_eval_rows;
+  gm_ac_traj t{};
+  t.capacity = 1;
+  t.obs = f; f += n * n_obs;
+  t.act = f; f += n * na;
+  t.mu = f; f += n * na;
+  t.logp = f; f += n;
+  t.val = f; f += n;
+  t.rew = f; f += n;
+  t.boot = f; f += n;
+  t.last_val = f;
+  t.end = p->d_eval_end;
+  if (chunk_queue_on(c)) {
+    GaArgs A{};
+    ac_fill(A, p, &t, sample, 0.0f, seed, decision0);
+    A.one_row = 1;
+    rc = stage_upload(c, p->d_args, &A, sizeof(GaArgs));
+    if (rc != GM_OK) return rc;
+    GmRolloutJob job = rollout_job(c, max_episode_steps, GM_DRV_AC, seed, 0.0f, max_episode_steps, nullptr);
+    job.ac = p->d_args;
+    return eval_launch(c, job, active, out);
+  }
+  return per_step_evaluate(c, max_episode_steps, active, out,
+                           [&](int k) { return gm_ac_act(p, &t, 0, sample, 0.0f, seed, decision0 + (uint64_t)k); });
 }
 
 int gm_ac_gae(gm_ctx* c, const gm_ac_traj* traj, int n_steps, float gamma, float lam, float* adv, float* ret) {
@@ -2708,6 +2870,33 @@ int gm_sac_rollout(gm_sac* p, int n_steps, int mode, uint64_t seed, uint64_t dec
       [&](int k) {
         return replay ? gm_sac_push_end(p, replay, row0 + (int64_t)k * c->n_envs, max_episode_steps) : (int)GM_OK;
       });
+}
+
+int gm_sac_evaluate(gm_sac* p, int mode, uint64_t seed, uint64_t decision0, int max_episode_steps,
+                    const uint8_t* active, const gm_eval_out* out) {
+  if (!p || !p->ctx) return GM_E_ARG;
+  gm_ctx* c = p->ctx;
+  if (!sac_mode_ok(mode))
+    return fail(c, GM_E_ARG, "gm_sac_evaluate: mode must be GM_SAC_MEAN, GM_SAC_SAMPLE or GM_SAC_RANDOM");
+  int rc = eval_action_kind(c, "gm_sac_evaluate", true, "the SAC actor");
+  if (rc == GM_OK) rc = eval_check(c, "gm_sac_evaluate", max_episode_steps, out);
+  if (rc != GM_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (chunk_queue_on(c)) {
+    GsArgs A{};   // (rep.state == NULL: the driver records nothing)
+    A.net = p->net;
+    A.params = p->d_params;
+    A.mode = mode;
+    A.seed = seed;
+    A.decision0 = decision0;
+    rc = stage_upload(c, p->d_args, &A, sizeof(GsArgs));
+    if (rc != GM_OK) return rc;
+    GmRolloutJob job = rollout_job(c, max_episode_steps, GM_DRV_SAC, seed, 0.0f, max_episode_steps, nullptr);
+    job.sac = p->d_args;
+    return eval_launch(c, job, active, out);
+  }
+  return per_step_evaluate(c, max_episode_steps, active, out,
+                           [&](int k) { return gm_sac_act(p, mode, seed, decision0 + (uint64_t)k); });
 }
 
 int gm_sac_replay_sample(gm_ctx* c, const gm_sac_replay* replay, int64_t size, int batch, uint64_t seed, uint64_t draw,

@@ -44,6 +44,11 @@ struct GmRolloutJob {
   };
   const GrArgs* replay;      // GM_DRV_DQN: device copy of the replay memory to record into (NULL: none);
                              // GM_DRV_SAC: the same with a NULL action, for the second half of its push
+  // an evaluation launch (gm_evaluate and the like; DESIGN.md §5, "Evaluation launch"; the EVAL
+  // instantiations of the kernel): an env whose episode ends writes its report into ev and
+  // retires instead of being reset.  Not read by the other kernels.
+  const uint8_t* active;     // [n_envs] envs that take part (NULL: all); the others finish at their fresh pick
+  gm_eval_out ev;
 };
 struct GmChunkCarry {        // what a chunk hands the next besides the hot state
   int32_t sub_done, nsub;

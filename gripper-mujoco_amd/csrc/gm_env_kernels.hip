@@ -141,6 +141,29 @@ extern "C" __global__ void gm_autoreset_mask_kernel(const GmEnvState* __restrict
   if (episodes) episodes[env] = e;
 }
 
+// gm_eval_record, one wave per env: a still-active env whose episode has ended writes its test
+// report (eval_report, the evaluation launch's own) and clears its active byte.  init != 0 is the
+// entry points' first call, before any env-step: every inactive env's end becomes 0, nothing else.
+extern "C" __global__ __launch_bounds__(64) void gm_eval_record_kernel(const GmEnvState* __restrict__ states,
+                                                                       const uint8_t* __restrict__ done, int max_steps,
+                                                                       uint8_t* __restrict__ active, gm_eval_out out,
+                                                                       int n_envs, int init) {
+  const int env = blockIdx.x;
+  if (env >= n_envs) return;
+  const int lane = threadIdx.x;
+  if (init) {
+    if (lane == 0 && !active[env]) out.end[env] = 0;
+    return;
+  }
+  if (!active[env]) return;
+  const GmEnvState& s = states[env];
+  const int end = gm_episode_end_code(done[env], s.num_action_steps, max_steps);
+  if (!end) return;
+  eval_report(s, out, env, end, lane);
+  __syncthreads();   // every lane has read the byte before lane 0 clears it
+  if (lane == 0) active[env] = 0;
+}
+
 // One wave per env (grid = n_envs workgroups of 64; unmasked envs exit at once): the new
 // record's hot part is built in LDS (lane 0's serial reset reads back what it wrote many
 // times over) and stored to HBM in one coalesced sweep; the sensor windows are cleared in

@@ -78,7 +78,7 @@ __device__ __forceinline__ void duo_helper(SharedT<CL>& S, const gm_model* __res
     __syncthreads();
   }
 }
-template <int CL, bool CAL, bool DUO>
+template <int CL, bool CAL, bool DUO, bool EVAL = false>
 __device__ __forceinline__ void step_kernel_body(SharedT<CL>& S,
     GmEnvState* __restrict__ states, const gm_model* __restrict__ m, const gm_config* __restrict__ C,
     const GmTopo* __restrict__ T, float* __restrict__ obs, float* __restrict__ rew,
@@ -86,10 +86,11 @@ __device__ __forceinline__ void step_kernel_body(SharedT<CL>& S,
     uint32_t* __restrict__ cost, const GmChunkQ& q, int lane) {
   if constexpr (!CAL) {
     if (q.chunk > 0) {   // chunked work queue (gm_step): the grid is the resident wave slots
-      chunked_env_steps<CL, DUO>(S, states, m, C, T, obs, rew, done, n_envs, order, cost, q, lane);
+      chunked_env_steps<CL, DUO, EVAL>(S, states, m, C, T, obs, rew, done, n_envs, order, cost, q, lane);
       return;
     }
   }
+  if constexpr (EVAL) return;   // (an evaluation launch is a queue launch: gm_eval.hip)
   if ((int)blockIdx.x >= n_envs) return;
   // cost-sorted dispatch: workgroups start in blockIdx order, so the envs that were the
   // most expensive last env-step are started first (longest-processing-time list
@@ -173,7 +174,8 @@ __device__ __forceinline__ void step_kernel_body(SharedT<CL>& S,
                                        S.work_mpr, S.work_newton);
   store_state(S, states + env, lane);
 }
-template <int CL, bool CAL, bool DUO = false>
+// EVAL: the evaluation launch's instantiations (gm_eval.hip; chunked_env_steps)
+template <int CL, bool CAL, bool DUO = false, bool EVAL = false>
 __global__ __launch_bounds__(DUO ? 2 * NT : NT, GM_WPS) void gm_step_kernel(
     GmEnvState* __restrict__ states, const gm_model* __restrict__ m, const gm_config* __restrict__ C,
     const GmTopo* __restrict__ T, float* __restrict__ obs, float* __restrict__ rew,
@@ -187,7 +189,7 @@ __global__ __launch_bounds__(DUO ? 2 * NT : NT, GM_WPS) void gm_step_kernel(
       return;
     }
   }
-  step_kernel_body<CL, CAL, DUO>(S, states, m, C, T, obs, rew, done, n_envs, mode, dbg, order, cost, q, (int)threadIdx.x);
+  step_kernel_body<CL, CAL, DUO, EVAL>(S, states, m, C, T, obs, rew, done, n_envs, mode, dbg, order, cost, q, (int)threadIdx.x);
   if constexpr (DUO) {
     // every path of the owner wave ends here: release the helper
     if (threadIdx.x == 0) S.duo_cmd = 0;

@@ -125,7 +125,8 @@ __device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restri
     return;
   }
   const GaArgs& A = *Ap;
-  const size_t row = (size_t)k * (size_t)n_envs + (size_t)env;
+  // (an evaluation launch writes every env-step into the evaluator's one scratch row; the draws keep k)
+  const size_t row = A.one_row ? (size_t)env : (size_t)k * (size_t)n_envs + (size_t)env;
   if (phase == 0) {
     const int n_obs = A.net.actor.width[0];
     const int na = A.net.actor.width[A.net.actor.n_layers];
@@ -180,22 +181,52 @@ __device__ __noinline__ void ac_rollout_driver(int phase, const GaArgs* __restri
   }
 }
 
+// One env's test report (gm_eval_out) from its state s at the episode's end (end: its
+// gm_episode_end_code), one event column per lane: gm_get_event_rows' values and column order.
+// The evaluation launch (rollout_end_step) and gm_eval_record's kernel both call this.
+__device__ __noinline__ void eval_report(const GmEnvHot& s, const gm_eval_out o, int env, int end, int lane) {
+  const int W = GM_N_BINARY + GM_N_LINEAR;
+  for (int c = lane; c < W; c += 64) {
+    const size_t i = (size_t)env * W + c;
+    if (c < GM_N_BINARY) {
+      o.rows[i] = s.bev_row[c]; o.abs[i] = s.bev_abs[c]; o.last[i] = (float)s.bev_last[c];
+    } else {
+      o.rows[i] = s.lev_row[c - GM_N_BINARY]; o.abs[i] = s.lev_abs[c - GM_N_BINARY];
+      o.last[i] = s.lev_last[c - GM_N_BINARY];
+    }
+  }
+  if (lane == 0) {
+    o.ret[env] = s.cumulative_reward;
+    o.length[env] = s.num_action_steps;
+    o.end[env] = (uint8_t)end;
+  }
+}
+
 // Where the drivers plug into the queue's env-steps ("The seam between the queue
 // and the drivers"): one env of job J on its wave, its state in the LDS image S, g its HBM record;
 // scratch: the union S.st.  (The begin of an env-step is in chunked_env_steps: a function cost a VGPR.)
 __device__ __forceinline__ int64_t rollout_gid(const GmRolloutJob& J, int env) { return J.sr.env_offset + env; }
 // End env-step k, after the epilogue: gm_autoreset_episodes on this env -- the episode-end
 // record, the actor-critic's trajectory record or the DQN replay memory's second half (gm_replay.h
-// replay_record), then MjEnv.reset and the reset observation
-template <int CL>
-__device__ __forceinline__ void rollout_end_step(SharedT<CL>& S, GmEnvState* g, float* __restrict__ obs, int env,
+// replay_record), then MjEnv.reset and the reset observation.  In an evaluation launch (EVAL)
+// an env whose episode ended writes its test report instead, is not reset, and the call returns
+// nonzero: the env retires (chunked_env_steps ends its job there).  Returns 0 otherwise.
+template <int CL, bool EVAL>
+__device__ __forceinline__ int rollout_end_step(SharedT<CL>& S, GmEnvState* g, float* __restrict__ obs, int env,
                                                  int n_envs, const GmRolloutJob& J, int k, const gm_model* __restrict__ m,
                                                  const gm_config* __restrict__ C, const GmTopo* __restrict__ T, int lane) {
-  if (J.driver < 0) return;
+  if (J.driver < 0) return 0;
   const int end = __builtin_amdgcn_readfirstlane(gm_episode_end_code(S.s.done, S.s.num_action_steps, J.max_ep));
   if (lane == 0 && J.rec)
     J.rec[(size_t)k * (uint32_t)n_envs + env] =
         gm_episode_end_record(end, S.s.cumulative_reward, S.s.num_action_steps, S.s.bev_last[GM_EV_successful_grasp]);
+  if constexpr (EVAL) {   // (nothing is recorded: no trajectory record, no replay memory)
+    if (end) {
+      GM_ENV_SYNC();   // lane 0's epilogue writes (the event rows) before the lanes read their columns
+      eval_report(S.s, J.ev, env, end, lane);
+    }
+    return end;   // no reset: the env retires where its episode ended
+  }
   if (J.driver == GM_DRV_AC)
     ac_rollout_driver(1, J.ac, obs + (size_t)env * C->n_obs, env, n_envs, k, J.max_ep, rollout_gid(J, env),
                       reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
@@ -210,21 +241,24 @@ __device__ __forceinline__ void rollout_end_step(SharedT<CL>& S, GmEnvState* g, 
               sh_pxy, sh_pxy + GM_SPAWN_MAX_XY, lane);
     get_obs_lanes(S.s, g->ring, C, obs + (size_t)env * C->n_obs, lane);
   }
+  return 0;
 }
 // Finish the job after its last env-step (k_end = J.steps): the actor-critic's last value
-template <int CL>
+// (an evaluation keeps no trajectory: none)
+template <int CL, bool EVAL>
 __device__ __forceinline__ void rollout_finish(SharedT<CL>& S, GmEnvState* g, float* __restrict__ obs, int env,
                                                int n_envs, const GmRolloutJob& J, int k_end, const gm_model* __restrict__ m,
                                                const gm_config* __restrict__ C, int lane) {
-  if (J.driver == GM_DRV_AC)
+  if (!EVAL && J.driver == GM_DRV_AC)
     ac_rollout_driver(2, J.ac, obs + (size_t)env * C->n_obs, env, n_envs, k_end, J.max_ep, rollout_gid(J, env),
                       reinterpret_cast<float*>(&S.st), S.s, m, C, lane);
 }
 
 // the persistent loop of gm_step_kernel's chunked mode (a mode of the one kernel, not a
 // kernel of its own: substep_loop keeps its single caller and so its constant LDS base): take
-// work; load state and carry; per env-step actions, substeps, epilogue, end; finish or yield
-template <int CL, bool DUO>
+// work; load state and carry; per env-step actions, substeps, epilogue, end; finish or yield.
+// EVAL: the evaluation launch ("Evaluation launch"), instantiated in gm_eval.hip.
+template <int CL, bool DUO, bool EVAL = false>
 __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __restrict__ states,
                                                   const gm_model* __restrict__ m, const gm_config* __restrict__ C,
                                                   const GmTopo* __restrict__ T, float* __restrict__ obs,
@@ -251,6 +285,21 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
     const unsigned long long t_start = __builtin_amdgcn_s_memtime();
     // lane 0's acquire load saw the entry: extend it to the whole wave's loads of the state
     if (!pick.fresh) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (EVAL && pick.fresh && J.active && !J.active[env]) {
+      // an evaluation's inactive env (only ever a fresh pick: it never yields) finishes at once:
+      // no state is loaded, no env-step runs, its cost slot keeps the last launch's value; the
+      // diagnostics show a job of no clocks and no yields that ended when it was picked
+      if (lane == 0) {
+        J.ev.end[env] = 0;
+        __hip_atomic_store(&q.carry[env].clk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&q.carry[env].job_yields, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        add_agent(cq_counter(q, GM_CQC_DONE), 1u);
+        st_agent(env_t + 1, tp);
+        __hip_atomic_fetch_max(q.st + GM_CQT_LAST_DONE, tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      last_end = tp;
+      continue;
+    }
     GmEnvState* g = states + env;
     load_state(S, g, lane);
     GmChunkCarry cr;
@@ -317,11 +366,12 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
       if (cr.sub_done < cr.nsub) break;   // yielded
       unsigned long long t0 = 0;
       env_step_epilogue(S, m, C, T, obs, rew, done, env, lane, false, t0);
-      rollout_end_step(S, g, obs, env, n_envs, J, cr.step_idx, m, C, T, lane);
+      // (an evaluation's env whose episode ended retires: this was its job's last env-step)
+      if (rollout_end_step<CL, EVAL>(S, g, obs, env, n_envs, J, cr.step_idx, m, C, T, lane)) cr.steps_left = 1;
       cr.steps_left -= 1;
       cr.step_idx += 1;
       if (cr.steps_left <= 0) {
-        rollout_finish(S, g, obs, env, n_envs, J, cr.step_idx, m, C, lane);
+        rollout_finish<CL, EVAL>(S, g, obs, env, n_envs, J, cr.step_idx, m, C, lane);
         finished = true;
         break;
       }
@@ -332,8 +382,10 @@ __device__ __forceinline__ void chunked_env_steps(SharedT<CL>& S, GmEnvState* __
     if (finished) {
       if (cost && lane == 0) {
         const uint32_t clk = cr.clk + (uint32_t)((__builtin_amdgcn_s_memtime() - t_start) >> 6);
-        // for the next launch's order, per env-step (whatever its job length)
-        cost[w.n + env] = dispatch_cost(clk, (uint32_t)cq_job_scale(q), S.work_nefc, S.work_mpr, S.work_newton);
+        // for the next launch's order, per env-step actually run: cr.step_idx, the job's length
+        // except where an evaluation's env retired early
+        cost[w.n + env] = dispatch_cost(clk, (uint32_t)(EVAL ? cr.step_idx : cq_job_scale(q)), S.work_nefc, S.work_mpr,
+                                        S.work_newton);
         // diagnostics (gm_chunk_job_stats): the job's busy clocks / 64 and its yields
         __hip_atomic_store(&q.carry[env].clk, clk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&q.carry[env].job_yields, cr.job_yields, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

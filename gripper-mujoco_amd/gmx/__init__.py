@@ -15,6 +15,7 @@ from .policy import DevicePolicy, DeviceLearner, ReplayBuffer, eps_threshold, dq
 from .ppo import DeviceActorCritic, DeviceCategoricalActorCritic, TrajectoryBuffer, DevicePPOLearner, ppo_opt, ppo_opt_default
 from .sac import DeviceSAC, ActionReplayBuffer, DeviceSACLearner, SAC_DEFAULTS, sac_options, sac_opt
 from .scripted import GraspScript, in_use_actions
+from .eval import Evaluator, test_plan, test_performance, new_report, EVENT_NAMES
 
 __all__ = ["load_library", "Settings", "ModelParams", "Object", "Spawn", "SpawnParams", "default_spawn_params",
            "Calibration", "calibrate", "CAL_TIMESTEP", "CAL_GAUGES", "CAL_REFERENCE_RETRY",
@@ -25,4 +26,5 @@ __all__ = ["load_library", "Settings", "ModelParams", "Object", "Spawn", "SpawnP
            "DeviceLearner", "dqn_opt", "dqn_opt_default",
            "DeviceActorCritic", "DeviceCategoricalActorCritic", "TrajectoryBuffer", "DevicePPOLearner", "ppo_opt", "ppo_opt_default",
            "DeviceSAC", "ActionReplayBuffer", "DeviceSACLearner", "SAC_DEFAULTS", "sac_options", "sac_opt",
-           "GraspScript", "in_use_actions", "env_state_dtype", "env_state_view"]
+           "GraspScript", "in_use_actions", "env_state_dtype", "env_state_view",
+           "Evaluator", "test_plan", "test_performance", "new_report", "EVENT_NAMES"]

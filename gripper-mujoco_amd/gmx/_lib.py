@@ -345,6 +345,11 @@ def _declare(lib):
         "gm_set_motor_target": (i32, [vp, vp, vp, i32, vp]),
         "gm_random_actions": (i32, [vp, C.c_uint64, vp, i32]),
         "gm_rollout": (i32, [vp, i32, vp, vp]),
+        "gm_evaluate": (i32, [vp, vp, vp, vp]),
+        "gm_eval_record": (i32, [vp, i32, vp, vp]),
+        "gm_policy_evaluate": (i32, [vp, C.c_uint64, C.c_uint64, i32, vp, vp]),
+        "gm_ac_evaluate": (i32, [vp, i32, C.c_uint64, C.c_uint64, i32, vp, vp]),
+        "gm_sac_evaluate": (i32, [vp, i32, C.c_uint64, C.c_uint64, i32, vp, vp]),
         "gm_get_sensor_si": (i32, [vp, vp]),
         "gm_set_random_spawn": (i32, [vp, i32, C.c_uint64, i32, i32]),
         "gm_scripted_actions": (i32, [vp, C.c_uint64, C.c_float, vp, i32]),

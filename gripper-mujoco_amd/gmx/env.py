@@ -222,6 +222,19 @@ class BatchedGripperEnv:
         p.action_mode, p.max_episode_steps, p.seed, p.jitter = int(action_mode), int(mx), int(seed), float(jitter)
         self._check(self.lib.gm_rollout(self._ctx, int(n_steps), C.byref(p), C.c_void_p(records_dev_ptr or 0)))
 
+    def evaluate(self, action_mode: int = 3, seed: int = 1234, jitter: float = 0.2,
+                 max_episode_steps: int | None = None, active=None, out=None) -> dict:
+        """gm_evaluate: one episode per active env under a scripted driver (rollout's action
+        modes; 3, the grasp program, is Trainer.test(heuristic=True)), each env retiring at its
+        episode's end; the test report as device tensors (gmx.eval).  Reset before reuse."""
+        from .eval import env_evaluate
+        return env_evaluate(self, action_mode, seed, jitter, max_episode_steps, active, out)
+
+    def eval_record(self, active, out, max_episode_steps: int | None = None):
+        """gm_eval_record, the per-step half of evaluate (gmx.eval.env_eval_record)."""
+        from .eval import env_eval_record
+        env_eval_record(self, active, out, max_episode_steps)
+
     def set_motor_target(self, xyz, mask=None):
         """MjClass::set_motor_target(x, y, z) (bind.cpp:82) for every env (xyz: 3 values, or
         [n_envs, 3]); returns the reference's in-limits flags per env."""

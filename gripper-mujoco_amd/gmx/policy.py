@@ -290,6 +290,13 @@ class DevicePolicy:
                                                C.c_uint64(decision0), int(mx), C.c_void_p(records_dev_ptr or 0)),
                     "gm_policy_rollout")
 
+    def evaluate(self, seed: int = 0, decision0: int = 0, max_episode_steps: int | None = None, active=None,
+                 out=None) -> dict:
+        """gm_policy_evaluate: one greedy episode per active env, each env retiring at its episode's
+        end; the test report as device tensors (gmx.eval).  Reset the env before reuse."""
+        from .eval import policy_evaluate
+        return policy_evaluate(self, seed, decision0, max_episode_steps, active, out)
+
     def read(self):
         n, a = self.env.n_envs, self.env.n_actions
         acts = np.zeros(n, dtype=np.int32)

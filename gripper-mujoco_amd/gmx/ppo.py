@@ -319,6 +319,15 @@ class DeviceActorCritic:
                                            C.c_uint64(decision0), int(mx), C.c_void_p(records_dev_ptr or 0)),
                     "gm_ac_rollout")
 
+    def evaluate(self, sample: bool = True, seed: int = 0, decision0: int = 0, max_episode_steps: int | None = None,
+                 active=None, out=None) -> dict:
+        """gm_ac_evaluate: one episode per active env, each env retiring at its episode's end
+        (sample=True: the reference's PPO test mode, which still samples; False: mean / argmax); the
+        test report as device tensors (gmx.eval).  No TrajectoryBuffer is written.  Reset the env
+        before reuse."""
+        from .eval import ac_evaluate
+        return ac_evaluate(self, sample, seed, decision0, max_episode_steps, active, out)
+
     def gae(self, traj: TrajectoryBuffer, gamma: float = 0.99, lam: float = 0.97, n_steps: int | None = None):
         return traj.gae(gamma, lam, n_steps)
 

@@ -365,6 +365,13 @@ class DeviceSAC:
         if replay is not None:
             replay.pushed += int(n_steps) * self.env.n_envs
 
+    def evaluate(self, mode="mean", seed: int = 0, decision0: int = 0, max_episode_steps: int | None = None,
+                 active=None, out=None) -> dict:
+        """gm_sac_evaluate: one episode per active env, each env retiring at its episode's end; the
+        test report as device tensors (gmx.eval).  No memory is written.  Reset the env before reuse."""
+        from .eval import sac_evaluate
+        return sac_evaluate(self, mode, seed, decision0, max_episode_steps, active, out)
+
     @staticmethod
     def _f32_dev(t, shape, name):
         import torch

@@ -1204,6 +1204,68 @@ int  gm_sac_learner_train(gm_sac_learner* l, gm_sac* target, const gm_sac_replay
                           uint64_t seed, uint64_t noise_seed, uint64_t draw0, int n_updates, float gamma, float alpha,
                           int bootstrap_truncated, float tau, float* losses);
 
+/* ---- batched evaluation: one test episode per env, then the env retires (DESIGN.md §5,
+ * "Evaluation launch") ----
+ * MujocoTrainer.test() runs every test episode to its end and keeps MjEnv._monitor_test's
+ * test report of it (the cumulative reward and the event track).  An evaluation launch does that
+ * for every active env at once: each runs from its current state until its episode ends
+ * (gm_episode_end_code: 1 done, 2 truncated at num_action_steps >= max_episode_steps, so at
+ * most max_episode_steps env-steps wherever the env started), writes its report and leaves the
+ * work queue; the launch ends with the last episode.  Nothing is reset and nothing is recorded
+ * into a trajectory buffer or a replay memory.
+ *
+ * The report, device arrays, one row per env (W = binary + linear events in gm_get_event_rows'
+ * column order): what gm_get_event_rows and the state record hold at the episode's last
+ * env-step before any reset, i.e. MjClass::get_test_report plus MjEnv.track.cumulative_reward.
+ * An inactive env gets end = 0 and its other rows are not touched. */
+typedef struct gm_eval_out {
+  float*   ret;      /* [n_envs] cumulative_reward at the episode's end                        */
+  int32_t* length;   /* [n_envs] num_action_steps at the end                                   */
+  uint8_t* end;      /* [n_envs] gm_episode_end_code (1 done, 2 truncated); 0: env not active  */
+  int32_t* rows;     /* [n_envs x W]                                                           */
+  int32_t* abs;      /* [n_envs x W]                                                           */
+  float*   last;     /* [n_envs x W]                                                           */
+} gm_eval_out;
+/* The per-step half: after a gm_step, every env with active_inout[e] != 0 whose episode has ended
+ * writes its report and clears its active byte (active_inout: device [n_envs], required).  With
+ * it the evaluation launches below have the per-step sequence every fused launch here has,
+ *   act -> gm_step -> gm_eval_record -> gm_autoreset_episodes(max_episode_steps, spawn = NULL),
+ * max_episode_steps times: envs that have reported carry on into later episodes and are ignored.
+ * Envs are independent, so the reports are bit for bit the fused launch's; that sequence is also
+ * what the entry points run when the queue is off (GM_CHUNK_SUBSTEPS=0), on a private copy of
+ * active (the caller's array is never written by them), after setting end = 0 for every inactive env. */
+int  gm_eval_record(gm_ctx* ctx, int max_episode_steps, uint8_t* active_inout, const gm_eval_out* out);
+/* The evaluation launches.  active: device [n_envs] bytes, NULL = every env.  out: every array
+ * required.  max_episode_steps <= 0 (the launch would be unbounded), a NULL out or a missing
+ * array are GM_E_ARG with a gm_last_error text, and nothing is launched.
+ *   gm_evaluate         the scripted drivers, params->action_mode 0, 1, 3 or 4 (3, the grasp
+ *                       program, is Trainer.test(heuristic=True)); params->max_episode_steps bounds it
+ *   gm_policy_evaluate  the DQN policy, greedy (eps = 0)
+ *   gm_ac_evaluate      both actor kinds; sample = 1 is the reference's PPO test mode, which still
+ *                       samples (noise is 0), sample = 0 the mean / the argmax.  The actor-critic
+ *                       handle owns the one-row scratch trajectory the actor's phases write into
+ *   gm_sac_evaluate     mode GM_SAC_MEAN is the test mode; GM_SAC_SAMPLE / GM_SAC_RANDOM are accepted
+ * An agent's handle needs the action kind it was created for: the creators refuse the other kind,
+ * and where gm_update_config has changed continous_actions since, the three agent calls return
+ * GM_E_ARG with a gm_last_error text and launch nothing.  A NULL handle is GM_E_ARG.
+ * An inactive env shows in the launch's diagnostics as a job of 0 clocks and 0 yields
+ * (gm_chunk_job_stats) that finished at the moment it was picked (gm_chunk_timeline).
+ * The reports are a deterministic function of the env states and the arguments at the call.  The
+ * env state after the call is NOT specified beyond that: the fused launch leaves every active env
+ * parked at its terminal state (episode not advanced, num_action_steps = length), the per-step
+ * sequence leaves it somewhere in a later episode.  Reset before reuse (gm_reset).
+ * gm_last_step_ms then times the whole launch, and its per-env-step divisor, gm_dispatch_info
+ * out[3], is max_episode_steps: an upper bound of the env-steps an env ran, so ms / out[3] is a
+ * lower bound of the time per env-step; for envs that started at a reset, out->length summed over
+ * the active envs is the number of env-steps the launch ran. */
+int  gm_evaluate(gm_ctx* ctx, const gm_rollout_params* params, const uint8_t* active, const gm_eval_out* out);
+int  gm_policy_evaluate(gm_policy* p, uint64_t seed, uint64_t decision0, int max_episode_steps, const uint8_t* active,
+                        const gm_eval_out* out);
+int  gm_ac_evaluate(gm_ac* p, int sample, uint64_t seed, uint64_t decision0, int max_episode_steps,
+                    const uint8_t* active, const gm_eval_out* out);
+int  gm_sac_evaluate(gm_sac* p, int mode, uint64_t seed, uint64_t decision0, int max_episode_steps,
+                     const uint8_t* active, const gm_eval_out* out);
+
 #ifdef __cplusplus
 }
 #endif
